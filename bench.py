@@ -83,7 +83,12 @@ def parse():
                     help="skip the Held-Karp 1-tree lower bounds (oracle/one_tree.c, host cores, after the timed region)")
     ap.add_argument("--exact_gap", action="store_true",
                     help="n <= 20: gap against the exact optimum (oracle/held_karp.c, host cores) instead of best-known")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (see dump_outputs())")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def instance_range(seed, n, lo, hi):
@@ -179,6 +184,37 @@ def time_to_gap(imp_cost, imp_time, imp_len, init_cost, best_known, targets, t_m
         ok = np.nonzero(gaps <= g)[0]
         out.append(float(grid[ok[0]]) if len(ok) else None)
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, gathered, r, seed):
+    """--dump-outputs: what the last timed step returned, as out_dir/<name>.npy, so that two builds can be compared output
+    for output on the same seeded instances.  gathered [total, 5] fp64 (every rank's instances after the one gather) gives
+    best_cost, init_cost, outer_iters, evals, status; this rank's SolveResult r gives best_tour [B, n+1], moves [B] and
+    regret_pred [B, n, n] (the GNN's guide, fp32).  Integers are stored exactly: tours as fp32, counters as fp64.  Above
+    DUMP_LIMIT_BYTES in all, the arrays of r keep a fixed seeded sample of its instances, whose indices are in sample_index.npy.
+    The search is wall-clock bounded (--time_limit), so best_cost / best_tour / outer_iters / evals / moves may differ
+    between two runs of the same build; regret_pred and init_cost are computed before the search and do not depend on it."""
+    os.makedirs(out_dir, exist_ok=True)
+    g = gathered.double().cpu().numpy()
+    arrays = {name: g[:, k].copy() for k, name in enumerate(("best_cost", "init_cost", "outer_iters", "evals", "status"))}
+    local = {"best_tour": r.best_tour.float(), "moves": r.moves.double()}
+    if r.regret_pred is not None:
+        local["regret_pred"] = r.regret_pred.float()
+    B = r.best_cost.shape[0]
+    per_instance = sum(t[0].numel() * t.element_size() for t in local.values()) if B else 0
+    room = DUMP_LIMIT_BYTES - sum(a.nbytes for a in arrays.values())
+    if B * per_instance > room:
+        keep = max(room, 0) // (per_instance + 8)                                # + 8: its entry of sample_index
+        idx = np.sort(np.random.default_rng(seed).choice(B, size=keep, replace=False))
+        arrays["sample_index"] = idx.astype(np.float64)
+        sel = torch.from_numpy(idx).to(r.best_cost.device)
+        local = {k: v.index_select(0, sel) for k, v in local.items()}
+    arrays.update({k: v.cpu().numpy() for k, v in local.items()})
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def physical_cores():
@@ -643,7 +679,7 @@ def main():
         nonlocal gathered
         r = pipeline.solve_batch(D, model, scalers, guides=args.guides, time_limit=args.time_limit,
                                  perturbation_moves=args.perturbation_moves, chunk=chunk_eff, budget=args.budget,
-                                 imp_cap=IMP_CAP)
+                                 imp_cap=IMP_CAP, keep_regret=args.dump_outputs is not None)
         local = torch.stack([r.best_cost, r.init_cost, r.outer_iters.double(), r.evals.double(),
                              r.status.double()], dim=1).contiguous()           # [B, 5] fp64
         if grouped and backend != "nccl":
@@ -687,6 +723,8 @@ def main():
     dt = time.time() - t0
     prof = _lib.profile_collect()
     _lib.profile_enable(False)
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, gathered, last, args.seed)
 
     stats_dev = "cuda" if backend == "nccl" else "cpu"
     t = torch.tensor([dt], dtype=torch.float64, device=stats_dev)

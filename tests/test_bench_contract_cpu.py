@@ -275,3 +275,42 @@ def test_best_known_files_cover_every_rank_of_an_eight_gpu_launch():
     assert b.load_best_known(None, 100, 2024, 0, 10000)[0] is not None
     assert b.load_best_known(None, 200, 2024, 0, 257)[0] is None                 # beyond the covered part of a block: no silent gaps
     assert b.load_best_known(None, 50, 2024, 0, 1024)[0] is not None
+
+
+def test_dump_outputs_of_the_last_step(tmp_path, monkeypatch):
+    """--dump-outputs: the arrays of the last timed step as DIR/<name>.npy (fp32 / fp64 only), every instance while they fit
+    the byte limit, else a fixed seeded sample of the per-instance arrays (sample_index.npy) that stays under it."""
+    import torch
+
+    from gnngls_amd.pipeline import SolveResult
+    b = bench_module()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "3", "--dump-outputs", str(tmp_path / "a")])
+    assert b.parse().steps == 3 and b.parse().dump_outputs == str(tmp_path / "a")
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        b.parse()
+    B, n = 40, 7
+    g = torch.Generator().manual_seed(0)
+    r = SolveResult(best_tour=torch.randint(0, n, (B, n + 1), dtype=torch.int32, generator=g),
+                    best_cost=torch.rand(B, dtype=torch.float64, generator=g), init_cost=torch.rand(B, dtype=torch.float64, generator=g),
+                    outer_iters=torch.arange(B), evals=torch.arange(B) * 7, moves=torch.arange(B, dtype=torch.int32),
+                    status=torch.zeros(B, dtype=torch.int32), regret_pred=torch.rand(B, n, n, dtype=torch.float64, generator=g))
+    gathered = torch.stack([r.best_cost, r.init_cost, r.outer_iters.double(), r.evals.double(), r.status.double()], 1)
+    b.dump_outputs(str(tmp_path / "a"), gathered, r, 2024)
+    out = {f[:-4]: np.load(os.path.join(tmp_path, "a", f)) for f in os.listdir(tmp_path / "a")}
+    assert set(out) == {"best_cost", "init_cost", "outer_iters", "evals", "status", "best_tour", "moves", "regret_pred"}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert np.array_equal(out["best_cost"], r.best_cost.numpy()) and np.array_equal(out["evals"], np.arange(B) * 7.0)
+    assert np.array_equal(out["best_tour"], r.best_tour.numpy()) and out["regret_pred"].shape == (B, n, n)
+    # a limit that holds only part of the instances: the same seeded sample every time, all arrays within the limit
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 5 * 8 * B + 10 * (4 * (n + 1) + 8 + 4 * n * n + 8))
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), gathered, r, 2024)
+    sizes = sum(os.path.getsize(os.path.join(tmp_path, "b", f)) - 128 for f in os.listdir(tmp_path / "b"))    # minus .npy headers
+    assert sizes <= b.DUMP_LIMIT_BYTES
+    idx = np.load(tmp_path / "b" / "sample_index.npy")
+    assert len(idx) == 10 and np.all(np.diff(idx) > 0) and np.array_equal(idx, np.load(tmp_path / "c" / "sample_index.npy"))
+    k = idx.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "b" / "best_tour.npy"), r.best_tour.numpy()[k])
+    assert np.array_equal(np.load(tmp_path / "b" / "regret_pred.npy"), r.regret_pred.float().numpy()[k])
+    assert np.load(tmp_path / "b" / "best_cost.npy").shape == (B,)

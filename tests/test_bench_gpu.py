@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -18,11 +19,18 @@ def last_json_line(out):
     return json.loads(lines[-1])
 
 
-def test_bench_single_rank_small():
+def test_bench_single_rank_small(tmp_path):
     # (one warm-up step: the first forward pass of a process loads the code objects, which would eat the 0.5 s budget)
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1",
-                                   "--batch", "64", "--time_limit", "0.5", "--cpu_cores", "8", "--no_gap_bracket"], cwd=ROOT, stderr=subprocess.STDOUT, timeout=600)
+                                   "--batch", "64", "--time_limit", "0.5", "--cpu_cores", "8", "--no_gap_bracket",
+                                   "--dump-outputs", str(tmp_path / "dump")], cwd=ROOT, stderr=subprocess.STDOUT, timeout=600)
     j = last_json_line(out)
+    # --dump-outputs: the arrays the timed step returned, the numbers of the line among them
+    d = {f[:-4]: np.load(os.path.join(tmp_path, "dump", f)) for f in os.listdir(tmp_path / "dump")}
+    assert d["best_cost"].shape == (64,) and d["best_tour"].shape == (64, 101) and d["regret_pred"].shape == (64, 100, 100)
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values()) and "sample_index" not in d
+    assert abs(d["best_cost"].mean() - j["mean_best_cost"]) < 1e-9 and abs(d["init_cost"].mean() - j["mean_init_cost"]) < 1e-9
+    assert (d["best_cost"] <= d["init_cost"]).all() and (np.sort(d["best_tour"][:, :-1], axis=1) == np.arange(100)).all()
     assert j["n_gpus"] == 1 and j["steps"] == 1 and j["warmup"] == 1 and j["unit"] == "instances/s"
     assert 64 / 1.5 < j["value"] < 64 / 0.45
     r = j["roofline"]
@@ -120,27 +128,28 @@ def run_ranks(nproc, port, extra, timeout=900):
     return last_json_line(subprocess.check_output(cmd, cwd=ROOT, env=env, stderr=subprocess.STDOUT, timeout=timeout))
 
 
-def test_bench_eight_ranks_configs3_in_miniature():
-    """The driver's 8-GPU launch of BASELINE configs[3] (a fixed test set cut into 8 contiguous shards, test.py:59), rehearsed
-    with 8 ranks sharing the one GPU over gloo: 1001 TSP20 instances -> shards of 126 x 7 + 119, two rounds of the full budget
-    per rank at a residency of 64, ONE gather per step, every rank bound to device local_rank % visible devices."""
-    j = run_ranks(8, 29541, ["--tsp_n", "20", "--total_instances", "1001", "--time_limit", "0.3", "--guides", "weight",
+def test_bench_four_ranks_configs3_in_miniature():
+    """The driver's multi-GPU launch of BASELINE configs[3] (a fixed test set cut into contiguous shards, test.py:59), rehearsed
+    with 4 ranks sharing the one GPU over gloo (not 8: with the test process that would be more than six processes holding the
+    one device): 501 TSP20 instances -> shards of 126 x 3 + 123, two rounds of the full budget per rank at a residency of 64,
+    ONE gather per step, every rank bound to device local_rank % visible devices."""
+    j = run_ranks(4, 29541, ["--tsp_n", "20", "--total_instances", "501", "--time_limit", "0.3", "--guides", "weight",
                              "--resident_instances", "64"])
     c = j["config"]
-    assert j["n_gpus"] == 8 and j["scaling"] == "strong" and c["total_instances"] == 1001 and c["world_size"] == 8
-    assert c["rounds_per_rank"] == [2] * 8 and c["collectives_per_step"] == {"gather": 1.0} and c["backend"] == "gloo"
-    assert c["device_of_rank"] == [r % c["visible_devices"] for r in range(8)]
+    assert j["n_gpus"] == 4 and j["scaling"] == "strong" and c["total_instances"] == 501 and c["world_size"] == 4
+    assert c["rounds_per_rank"] == [2] * 4 and c["collectives_per_step"] == {"gather": 1.0} and c["backend"] == "gloo"
+    assert c["device_of_rank"] == [r % c["visible_devices"] for r in range(4)]
     util = c["residency_utilisation"]
-    assert all(abs(u - 126 / 128) < 1e-12 for u in util[:7]) and abs(util[7] - 119 / 128) < 1e-12
-    assert 1001 / 3.0 < j["value"] < 1001 / 0.6 and j["watchdog_aborts"] == 0      # 2 rounds x 0.3 s, eight ranks on one GPU
-    assert len(j["gls_ms_per_rank"]) == 8 and j["roofline"]["launches"] == 2
+    assert all(abs(u - 126 / 128) < 1e-12 for u in util[:3]) and abs(util[3] - 123 / 128) < 1e-12
+    assert 501 / 3.0 < j["value"] < 501 / 0.6 and j["watchdog_aborts"] == 0      # 2 rounds x 0.3 s, four ranks on one GPU
+    assert len(j["gls_ms_per_rank"]) == 4 and j["roofline"]["launches"] == 2
 
 
-def test_bench_eight_ranks_configs4_in_miniature():
-    """BASELINE configs[4] per GPU (TSP200, weak scaling: rank r searches its own block, one round) with 8 ranks on the one
+def test_bench_four_ranks_configs4_in_miniature():
+    """BASELINE configs[4] per GPU (TSP200, weak scaling: rank r searches its own block, one round) with 4 ranks on the one
     GPU: 4 instances per rank, the 16-wave compact-store workgroups of TSP200."""
-    j = run_ranks(8, 29542, ["--tsp_n", "200", "--batch", "4", "--time_limit", "0.5", "--guides", "weight"])
+    j = run_ranks(4, 29542, ["--tsp_n", "200", "--batch", "4", "--time_limit", "0.5", "--guides", "weight"])
     c = j["config"]
-    assert j["n_gpus"] == 8 and j["scaling"] == "weak" and c["total_instances"] == 32 and c["instances_per_gpu"] == 4
-    assert c["rounds_per_rank"] == [1] * 8 and c["collectives_per_step"] == {"gather": 1.0}
-    assert 32 / 2.5 < j["value"] < 32 / 0.45 and j["watchdog_aborts"] == 0 and j["outer_iters_per_instance"] > 10
+    assert j["n_gpus"] == 4 and j["scaling"] == "weak" and c["total_instances"] == 16 and c["instances_per_gpu"] == 4
+    assert c["rounds_per_rank"] == [1] * 4 and c["collectives_per_step"] == {"gather": 1.0}
+    assert 16 / 2.5 < j["value"] < 16 / 0.45 and j["watchdog_aborts"] == 0 and j["outer_iters_per_instance"] > 10
