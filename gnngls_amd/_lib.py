@@ -51,6 +51,8 @@ SIGNATURES = {
     "gnngls_profile_enable": [_int],
     "gnngls_profile_collect": [_vp, _vp],
     "gnngls_profile_set_executed_evals": [_vp],
+    "gnngls_regret_labels_chunk": [_int],
+    "gnngls_regret_labels": [_vp, _int, _int, _vp, _vp, _int, _i64, _int, _f64, _int, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 PROF_KINDS = ["pack_features", "embed", "gemm_fc", "gat_rows", "gat_rows_rank1", "gemm_ffn1(unused)", "gemm_ffn2(unused)",

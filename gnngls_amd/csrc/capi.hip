@@ -8,11 +8,13 @@
 #include <string.h>
 
 #include <atomic>
+#include <functional>
 #include <mutex>
 #include <vector>
 
 #include "../../include/gnngls_hip.h"
 #include "gls_kernels.h"
+#include "labels_kernels.h"
 #include "model_kernels.h"
 #include "train_kernels.h"
 
@@ -367,6 +369,148 @@ int gnngls_gls_run(const double *D, const double *guides, int n_guides, int B, i
     if (asym) (void)hipFreeAsync(asym, st);
     if (ws) (void)hipFreeAsync(ws, st);
     return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "gls_run");
+}
+
+// ---- regret labels (datasets.py:23-34): chunks of fixed-edge jobs through gnngls_gls_run, see labels_kernels.h ----------------
+int gnngls_regret_labels_chunk(int n) {
+    if (n < 3 || n > 255) return 0;
+    int J = gnngls_gls_resident_capacity(n);           // one resident workgroup per job
+    if (J < 1) J = num_cus();
+    const long cap = (512L << 20) / ((long)n * n * sizeof(double));      // D' of a chunk <= 512 MiB
+    return (int)(J < cap ? J : cap);
+}
+
+int gnngls_regret_labels(const double *D, int B, int n, const int32_t *base_tour, const uint8_t *edge_mask,
+                         int perturbation_moves, int64_t max_outer_iters, int penalty_bits, double watchdog_s, int chunk_jobs,
+                         double *edge_cost, double *regret, int32_t *best_tour, double *best_cost, int32_t *status, void *stream) {
+    if (B == 0) return GNNGLS_OK;   // empty batch: nothing to enqueue (data pointers may be NULL)
+    if (!D || !base_tour || !edge_cost || !regret || !best_tour || !best_cost || !status || B < 0)
+        return fail(GNNGLS_ERR_ARG, "regret_labels: bad argument (NULL pointer or B < 0)");
+    if (n < 3 || n > 255) return fail(GNNGLS_ERR_ARG, "regret_labels: n=%d out of range (3..255)", n);
+    if (max_outer_iters < 0)
+        return fail(GNNGLS_ERR_ARG, "regret_labels: max_outer_iters must be >= 0 (labels are defined by an iteration count)");
+    if (perturbation_moves < 0) return fail(GNNGLS_ERR_ARG, "regret_labels: perturbation_moves must be >= 0");
+    if (!(watchdog_s > 0.0)) return fail(GNNGLS_ERR_ARG, "regret_labels: watchdog_s must be > 0");
+    if (penalty_bits != 0 && penalty_bits != 16 && penalty_bits != 32 && penalty_bits != -1 && penalty_bits != -2)
+        return fail(GNNGLS_ERR_ARG, "regret_labels: penalty_bits must be 0 (auto), 16, 32, -1 or -2");
+    if (chunk_jobs < 0) return fail(GNNGLS_ERR_ARG, "regret_labels: chunk_jobs must be >= 0 (0 = gnngls_regret_labels_chunk(n))");
+    hipStream_t st = (hipStream_t)stream;
+    const int n1 = n + 1, N = n * (n - 1) / 2;
+    // small per-instance workspace: M_b, base cost, rank of the best tour, asymmetry flags
+    char *ws = nullptr;
+    const size_t ws_bytes = (size_t)B * (3 * sizeof(double) + 2 * sizeof(int32_t));
+    hipError_t e = hipMallocAsync((void **)&ws, ws_bytes, st);
+    if (e != hipSuccess) return hip_fail(e, "regret_labels: workspace alloc");
+    double *offset = (double *)ws, *base_cost = offset + B;
+    int32_t *best_rank = (int32_t *)(base_cost + 2 * B), *asym = best_rank + B;
+    // the host builds the job lists: it needs the base tours (validated here) and the mask; an asymmetric D is rejected
+    std::vector<int32_t> tours_h((size_t)B * n1), asym_h(B);
+    std::vector<uint8_t> mask_h(edge_mask ? (size_t)B * N : 0);
+    e = gnngls::launch_symmetry_check(D, B, n, asym, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(asym_h.data(), asym, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(tours_h.data(), base_tour, tours_h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && edge_mask) e = hipMemcpyAsync(mask_h.data(), edge_mask, mask_h.size(), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { (void)hipFreeAsync(ws, st); return hip_fail(e, "regret_labels: reading the base tours"); }
+    std::vector<int32_t> pos((size_t)B * n);
+    for (int b = 0; b < B; ++b) {
+        const int32_t *t = &tours_h[(size_t)b * n1];
+        int32_t *pb = &pos[(size_t)b * n];
+        for (int v = 0; v < n; ++v) pb[v] = -1;
+        bool ok = t[0] == 0 && t[n] == 0;
+        for (int p = 0; ok && p < n; ++p) {
+            ok = t[p] >= 0 && t[p] < n && pb[t[p]] < 0;
+            if (ok) pb[t[p]] = p;
+        }
+        if (!ok) { (void)hipFreeAsync(ws, st); return fail(GNNGLS_ERR_ARG, "regret_labels: base_tour[%d] is not a tour from depot 0", b); }
+        if (asym_h[b]) {
+            (void)hipFreeAsync(ws, st);
+            return fail(GNNGLS_ERR_ARG, "regret_labels: D[%d] is not symmetric (a fixed edge is an undirected edge)", b);
+        }
+    }
+    e = gnngls::launch_label_offsets(D, B, n, offset, st);
+    if (e == hipSuccess) e = gnngls::launch_tour_cost(base_tour, D, B, n, base_cost, st);
+    if (e == hipSuccess)
+        e = gnngls::launch_label_init(B, n, base_tour, base_cost, edge_mask != nullptr, edge_cost, best_cost, best_rank, best_tour,
+                                      status, st);
+    if (e != hipSuccess) { (void)hipFreeAsync(ws, st); return hip_fail(e, "regret_labels: init"); }
+
+    // per-chunk workspace: jobs, D' (= the guide), start and returned tours, costs, search status
+    long total = 0;                                     // fixed-edge jobs of this call
+    for (int b = 0; b < B; ++b) {
+        const int32_t *pb = &pos[(size_t)b * n];
+        for (int i = 0, r = 0; i < n; ++i)
+            for (int j = i + 1; j < n; ++j, ++r) {
+                const int gap = abs(pb[i] - pb[j]);
+                total += gap != 1 && gap != n - 1 && (!edge_mask || mask_h[(size_t)b * N + r]);
+            }
+    }
+    if (total == 0) {
+        e = gnngls::launch_label_finalize(B, n, base_tour, base_cost, edge_cost, regret, st);
+        (void)hipFreeAsync(ws, st);
+        return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "regret_labels: finalize");
+    }
+    int J = chunk_jobs > 0 ? chunk_jobs : gnngls_regret_labels_chunk(n);
+    if (J > total) J = (int)total;
+    char *cw = nullptr;
+    const size_t dp_bytes = (size_t)J * n * n * sizeof(double);
+    const size_t cw_bytes = dp_bytes + (size_t)J * (sizeof(gnngls::LabelJob) + 2 * n1 * sizeof(int32_t) + 3 * sizeof(double) +
+                                                    sizeof(int32_t));
+    e = hipMallocAsync((void **)&cw, cw_bytes, st);
+    if (e != hipSuccess) { (void)hipFreeAsync(ws, st); return hip_fail(e, "regret_labels: chunk workspace alloc"); }
+    double *Dp = (double *)cw, *init_cost = Dp + (size_t)J * n * n, *search_cost = init_cost + J, *job_cost = search_cost + J;
+    gnngls::LabelJob *jobs_d = (gnngls::LabelJob *)(job_cost + J);
+    int32_t *tin = (int32_t *)(jobs_d + J), *tout = tin + (size_t)J * n1, *job_status = tout + (size_t)J * n1;
+    auto release = [&]() { (void)hipFreeAsync(cw, st); (void)hipFreeAsync(ws, st); };
+
+    // one chunk: expand, search, collect; then (16-bit counters) rerun the jobs that overflowed with 32-bit counters
+    std::vector<int32_t> status_h(J);
+    std::function<int(const std::vector<gnngls::LabelJob> &, int)> run = [&](const std::vector<gnngls::LabelJob> &jobs, int bits) {
+        const int cnt = (int)jobs.size();
+        hipError_t he = hipMemcpyAsync(jobs_d, jobs.data(), (size_t)cnt * sizeof(gnngls::LabelJob), hipMemcpyHostToDevice, st);
+        if (he == hipSuccess) he = gnngls::launch_label_expand(D, n, base_tour, jobs_d, cnt, offset, Dp, tin, st);
+        if (he == hipSuccess) he = gnngls::launch_tour_cost(tin, Dp, cnt, n, init_cost, st);
+        if (he != hipSuccess) return hip_fail(he, "regret_labels: expansion");
+        const int rc = gnngls_gls_run(Dp, Dp, 1, cnt, n, tin, init_cost, perturbation_moves, 0, bits, max_outer_iters, 0.0, watchdog_s,
+                                      tout, search_cost, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, job_status,
+                                      nullptr, nullptr, nullptr, 0, nullptr, stream);
+        if (rc != GNNGLS_OK) return rc;
+        he = gnngls::launch_label_collect(D, n, jobs_d, cnt, tout, job_status, job_cost, edge_cost, best_cost, best_rank, best_tour,
+                                          status, st);
+        if (he == hipSuccess) he = hipMemcpyAsync(status_h.data(), job_status, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+        if (he == hipSuccess) he = hipStreamSynchronize(st);      // (also: the host job list may be reused)
+        if (he != hipSuccess) return hip_fail(he, "regret_labels: labels");
+        std::vector<gnngls::LabelJob> again;
+        for (int k = 0; k < cnt; ++k)
+            if (status_h[k] == GNNGLS_STATUS_PENALTY_OVERFLOW) again.push_back(jobs[k]);
+        if (again.empty()) return (int)GNNGLS_OK;
+        if (bits != 0 && bits != 16) return fail(GNNGLS_ERR_HIP, "regret_labels: penalty overflow with %d-bit counters", bits);
+        return run(again, 32);
+    };
+    std::vector<gnngls::LabelJob> chunk;
+    chunk.reserve(J);
+    for (int b = 0; b < B; ++b) {
+        const int32_t *pb = &pos[(size_t)b * n];
+        for (int i = 0, r = 0; i < n; ++i)
+            for (int j = i + 1; j < n; ++j, ++r) {
+                const int gap = abs(pb[i] - pb[j]);
+                if (gap == 1 || gap == n - 1) continue;                 // on the base tour: regret 0
+                if (edge_mask && !mask_h[(size_t)b * N + r]) continue;  // kept from an earlier call
+                chunk.push_back(gnngls::LabelJob{b, i, j, r});
+                if ((int)chunk.size() == J) {
+                    const int rc = run(chunk, penalty_bits);
+                    if (rc != GNNGLS_OK) { release(); return rc; }
+                    chunk.clear();
+                }
+            }
+    }
+    if (!chunk.empty()) {
+        const int rc = run(chunk, penalty_bits);
+        if (rc != GNNGLS_OK) { release(); return rc; }
+    }
+    e = gnngls::launch_label_finalize(B, n, base_tour, base_cost, edge_cost, regret, st);
+    release();
+    return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "regret_labels: finalize");
 }
 
 }  // extern "C"

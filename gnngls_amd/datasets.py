@@ -7,7 +7,7 @@ Differences forced by the environment, none on the arithmetic:
   * networkx >= 3 removed read_gpickle (datasets.py:56,69): instances are read with pickle.load.
   * git-LFS pointer stubs (every file under the reference's data/ and models/) are detected and
     reported instead of failing inside pickle.
-Label generation (`set_labels`, needs LKH) is out of scope; `set_features` is kept.
+`set_features` is kept; `set_labels` labels on the device (gnngls_amd.labels: fixed-edge searches instead of LKH).
 """
 import pathlib
 import pickle
@@ -44,6 +44,49 @@ def set_features(G):
     """datasets.py:14-20"""
     for e in G.edges:
         G.edges[e]["features"] = np.array([G.edges[e]["weight"]], dtype=np.float32)
+
+
+def _tour_from_edges(G, flag="in_solution"):
+    """The tour from depot 0 through the edges flagged `flag`, or None if they do not form one Hamiltonian cycle."""
+    n = len(G.nodes)
+    adj = {v: [] for v in G.nodes}
+    for i, j, d in G.edges(data=True):
+        if d.get(flag):
+            adj[i].append(j)
+            adj[j].append(i)
+    if any(len(a) != 2 for a in adj.values()):
+        return None
+    tour, prev = [0], None
+    while len(tour) <= n:
+        a, b = adj[tour[-1]]
+        nxt = b if a == prev else a
+        prev = tour[-1]
+        tour.append(nxt)
+        if nxt == 0:
+            break
+    return tour if len(tour) == n + 1 and tour[-1] == 0 and len(set(tour)) == n else None
+
+
+def set_labels(G, **kwargs):
+    """datasets.py:23-34 on the device: regret = (cost - base) / base for every edge, cost = the true cost of the fixed-edge
+    search's tour (gnngls_amd.labels).  The base is G's `in_solution` tour when G has one (the reference's semantics:
+    `optimal_cost(G)`), else the default base of labels.regret_labels.  If a search finds a tour cheaper than the base,
+    `in_solution` is moved to the cheapest tour found, so that regret >= 0 and regret == 0 exactly on `in_solution`.
+    kwargs go to labels.regret_labels.  Returns the labels.LabelResult of the instance."""
+    from . import labels
+    n = len(G.nodes)
+    D = np.zeros((n, n), dtype=np.float64)
+    for i, j, d in G.edges(data=True):
+        D[i, j] = D[j, i] = d["weight"]
+    base = _tour_from_edges(G) if all("in_solution" in d for _, _, d in G.edges(data=True)) else None
+    res = labels.regret_labels(D[None], base_tour=None if base is None else [base], **kwargs)
+    regret = res.regret[0].cpu().numpy()
+    on = res.in_solution[0].cpu().numpy()
+    for e in G.edges:
+        r = labels.edge_rank(e[0], e[1], n)
+        G.edges[e]["in_solution"] = bool(on[r])
+        G.edges[e]["regret"] = 0. if on[r] else float(regret[r])
+    return res
 
 
 class TSPDataset(torch.utils.data.Dataset):

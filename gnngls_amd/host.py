@@ -38,3 +38,35 @@ def is_valid_tour(G, tour):
 def optimal_cost(G, weight="weight"):
     """Total weight of the edges flagged `in_solution`, in edge insertion order (reference __init__.py:55-60)."""
     return functools.reduce(operator.add, (d[weight] for _, _, d in G.edges(data=True) if d["in_solution"]), 0)
+
+
+def fixed_edge_tour(G, e, scale=None, lkh_path=None, base_tour=None, label_iters=None, perturbation_moves=None, **kwargs):
+    """A tour of G that holds edge e (reference __init__.py:63-79: LKH with e fixed).  Here: the fixed-edge search of
+    gnngls_amd.labels on the device -- guided_local_search on G's weights with e's weight lowered by M, guide = those weights,
+    from `base_tour` (default: G's `in_solution` tour, else labels.base_tours).  `scale`, `lkh_path` and LKH's keyword
+    arguments are accepted and ignored."""
+    import numpy as np
+    import torch
+
+    from . import labels, ops
+    from .datasets import _tour_from_edges
+    n = len(G.nodes)
+    D = np.zeros((n, n), dtype=np.float64)
+    for i, j, d in G.edges(data=True):
+        D[i, j] = D[j, i] = d["weight"]
+    if base_tour is None:
+        base_tour = _tour_from_edges(G) if all("in_solution" in d for _, _, d in G.edges(data=True)) else None
+    if base_tour is None:
+        base_tour = labels.base_tours(ops.as_dev(D[None], torch.float64))[0].tolist()
+    base_tour = [int(v) for v in base_tour]
+    if frozenset(e) in {frozenset(x) for x in _tour_edges(base_tour)}:
+        return base_tour
+    Dp = ops.as_dev(labels.fixed_edge_matrix(D, e[0], e[1])[None], torch.float64)
+    t0 = ops.as_dev([base_tour], torch.int32)
+    r = ops.gls_run(Dp, Dp[None].contiguous(), t0, ops.tour_cost(t0, Dp),
+                    perturbation_moves=labels.PERTURBATION_MOVES if perturbation_moves is None else perturbation_moves,
+                    max_outer_iters=labels.LABEL_ITERS if label_iters is None else label_iters)
+    tour = r.best_tour[0].tolist()
+    if frozenset(e) not in {frozenset(x) for x in _tour_edges(tour)}:
+        raise RuntimeError(f"fixed_edge_tour: the search lost edge {e} (status {int(r.status[0])})")
+    return tour

@@ -44,6 +44,8 @@ extern "C" {
                                          triangle (every store but the global-memory one): NOT searched -- best = the start tour,
                                          0 iterations -- because the reference reads D[a,b] as indexed (operators.py:25-28,97-102)
                                          and the search would differ; rerun the instance with penalty_bits = -1 */
+#define GNNGLS_STATUS_EDGE_LOST 4     /* gnngls_regret_labels: a fixed-edge search returned a tour without its edge (never expected:
+                                         see there); that edge keeps its earlier label */
 
 int gnngls_abi_version(void);
 const char *gnngls_last_error(void);
@@ -147,6 +149,36 @@ int gnngls_gls_run(const double *D, const double *guides, int n_guides, int B, i
                    double *trace_cost, float *trace_time, int trace_cap, int32_t *trace_len,
                    int32_t *penalty_out, int64_t *evals_out, int32_t *status,
                    double *imp_cost, float *imp_time, int64_t *imp_iter, int imp_cap, int32_t *imp_len, void *stream);
+
+/* ---- regret labels of the training data: datasets.set_labels (datasets.py:23-34) ----------------------------------------
+ * The reference labels every edge e outside the optimal tour with regret = (cost - opt) / opt, cost = tour_cost of the tour
+ * fixed_edge_tour (gnngls/__init__.py:63-79) returns: LKH with e forced into the tour.  Here that constrained solve is a
+ * FIXED-EDGE SEARCH: the reference's guided_local_search (algorithms.py:135-195) on the instance with one changed weight,
+ *     w'(i,j) = w'(j,i) = fl(D[i,j] - M_b),   M_b = the smallest power of two >= (2.0 n) * max(D_b)   (frexp / ldexp: exact),
+ * guides = ['weight'] on that matrix D' (the fixed edge has a negative utility and is never penalised), started from the base
+ * tour (which does not hold the edge), for exactly max_outer_iters outer iterations.  Every tour with the edge costs less under
+ * D' than every tour without it, and the first descent inserts it (a relocate move next to i is worth about -M), so the
+ * returned best tour holds the edge; its label is its TRUE cost (tour_cost on D, gnngls/__init__.py:17-21).
+ *   D            [B,n,n] fp64, bitwise symmetric (else GNNGLS_ERR_ARG); 3 <= n <= 255
+ *   base_tour    [B,n+1] a tour from depot 0 per instance (the reference's optimal tour; here the best tour known)
+ *   edge_mask    [B,N] uint8 or NULL.  NULL: every edge off the base tour gets a search; edge_cost is output only.
+ *                Else only the masked edges off the base tour get one, and edge_cost is IN/OUT: the results are min-merged into
+ *                it (the repair rounds of gnngls_amd.labels: costs of earlier calls are true costs of real tours with the edge)
+ *   perturbation_moves, max_outer_iters (>= 0), penalty_bits, watchdog_s: as gnngls_gls_run, per search; searches that end with
+ *                GNNGLS_STATUS_PENALTY_OVERFLOW are rerun with 32-bit counters
+ *   chunk_jobs   searches per launch of the search kernel (0 = gnngls_regret_labels_chunk(n)); each holds its own D' [n,n] in
+ *                stream-ordered workspace.  Results do not depend on it.
+ *   outputs      edge_cost [B,N]: base edges = the base tour's cost, other edges = min over the results they received;
+ *                regret [B,N] = (edge_cost - base_cost) / base_cost (datasets.py:31), exactly 0.0 on base edges -- NEGATIVE where a
+ *                search found a tour cheaper than the base (the caller then repairs the base, gnngls_amd.labels.regret_labels);
+ *                best_tour [B,n+1], best_cost [B]: the cheapest tour seen (the base or a search result; ties -> the base, then the
+ *                lowest edge index); status [B]: the most severe search status (GNNGLS_STATUS_WATCHDOG, GNNGLS_STATUS_EDGE_LOST)
+ * Bad arguments are rejected on the host before any device work.  The call synchronises the stream once per chunk (the host
+ * builds the job lists and reads the search statuses). */
+int gnngls_regret_labels_chunk(int n);
+int gnngls_regret_labels(const double *D, int B, int n, const int32_t *base_tour, const uint8_t *edge_mask,
+                         int perturbation_moves, int64_t max_outer_iters, int penalty_bits, double watchdog_s, int chunk_jobs,
+                         double *edge_cost, double *regret, int32_t *best_tour, double *best_cost, int32_t *status, void *stream);
 
 /* ---- K1/K2: edge-regret GNN forward ------------------------------------------------------------
  * EdgePropertyPredictionModel.forward (models.py:44-70) on the line graph of K_n (datasets.py:56-60),
