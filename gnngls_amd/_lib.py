@@ -39,6 +39,14 @@ SIGNATURES = {
     "gnngls_regret_train_workspace_bytes": [_int, _int, _int],
     "gnngls_regret_train_forward": [_vp, _vp, _int, _int, _int, _int, _f32, _vp, _vp, _vp, _i64, _vp],
     "gnngls_regret_train_backward": [_vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp, _i64, _vp],
+    "gnngls_model_heads_supported": [_int],
+    "gnngls_regret_forward_workspace_bytes_heads": [_int, _int, _int],
+    "gnngls_regret_forward_heads": [_vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _i64, _vp],
+    "gnngls_regret_prepare_heads": [_vp, _int, _int, _int, _vp, _i64, _vp],
+    "gnngls_regret_forward_prepared_heads": [_vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _vp, _vp, _i64, _vp],
+    "gnngls_regret_train_workspace_bytes_heads": [_int, _int, _int, _int],
+    "gnngls_regret_train_forward_heads": [_vp, _vp, _int, _int, _int, _int, _int, _f32, _vp, _vp, _vp, _i64, _vp],
+    "gnngls_regret_train_backward_heads": [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _i64, _vp],
     "gnngls_pack_features": [_vp, _int, _int, _f64, _f64, _vp, _vp],
     "gnngls_unpack_regret": [_vp, _int, _int, _f64, _f64, _vp, _vp],
     "gnngls_debug_set_penalty16_limit": [_int],
@@ -75,9 +83,15 @@ def profile_collect():
 _RESTYPES = {"gnngls_last_error": ctypes.c_char_p, "gnngls_model_packed_floats": ctypes.c_int64,
              "gnngls_regret_forward_workspace_bytes": ctypes.c_int64,
              "gnngls_regret_prepared_bytes": ctypes.c_int64,
-             "gnngls_regret_train_workspace_bytes": ctypes.c_int64}
+             "gnngls_regret_train_workspace_bytes": ctypes.c_int64,
+             "gnngls_regret_forward_workspace_bytes_heads": ctypes.c_int64,
+             "gnngls_regret_train_workspace_bytes_heads": ctypes.c_int64}
 
 _ABI4 = ("gnngls_regret_prepared_bytes", "gnngls_regret_prepare", "gnngls_regret_forward_prepared")
+# head counts other than 8 (an older build named by GNNGLS_HIP_SO lacks them; the 8-head path never calls them)
+_HEADS = ("gnngls_model_heads_supported", "gnngls_regret_forward_workspace_bytes_heads", "gnngls_regret_forward_heads",
+          "gnngls_regret_prepare_heads", "gnngls_regret_forward_prepared_heads", "gnngls_regret_train_workspace_bytes_heads",
+          "gnngls_regret_train_forward_heads", "gnngls_regret_train_backward_heads")
 _lib = None
 
 
@@ -100,7 +114,7 @@ def load():
         import torch  # noqa: F401
         L = ctypes.CDLL(SO)
         for name, argtypes in SIGNATURES.items():
-            if name in _ABI4 and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
+            if (name in _ABI4 or name in _HEADS) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
                 continue              # an older build of the library named by GNNGLS_HIP_SO (same-box A/B of kernel variants)
             f = getattr(L, name)      # AttributeError if the symbol is missing
             f.argtypes = argtypes

@@ -14,6 +14,7 @@
 
 #include "../../include/gnngls_hip.h"
 #include "gls_kernels.h"
+#include "heads_kernels.h"
 #include "labels_kernels.h"
 #include "model_kernels.h"
 #include "train_kernels.h"
@@ -521,6 +522,16 @@ int gnngls_regret_labels(const double *D, int B, int n, const int32_t *base_tour
 namespace {
 constexpr long kLayerFloats = 128L * 128 + 128 + 128 + 128 + 128 + 512L * 128 + 512 + 128L * 512 + 128 + 128 + 128;
 constexpr long kBytesPerNode = (128 + 128 + 256 + 32 + 128) * 4L;   // h, ft, part, part_ms, h2 (ping-pong)
+// 16 heads: + the per-head softmax statistics of both sides [2][16 + 16] (gat_heads_merge16_kernel's input)
+long bytes_per_node(int n_heads) { return kBytesPerNode + (n_heads == 16 ? 2 * 32 * 4L : 0); }
+
+int heads_fail(const char *what, int n_heads) {
+    return fail(GNNGLS_ERR_UNSUPPORTED, "%s: n_heads=%d is not supported (embed_dim 128: n_heads in {1, 2, 4, 8, 16})", what, n_heads);
+}
+
+int forward_prepared_impl(const float *feat, const float *weights, const void *prepared, int64_t prepared_bytes, int B, int n,
+                          int in_dim, int n_layers, int n_heads, float *y_out, void *workspace, int64_t workspace_bytes,
+                          void *stream);
 }  // namespace
 
 extern "C" {
@@ -567,13 +578,27 @@ int gnngls_regret_prepare(const float *weights, int in_dim, int n_layers, void *
 int gnngls_regret_forward_prepared(const float *feat, const float *weights, const void *prepared, int64_t prepared_bytes,
                                    int B, int n, int in_dim, int n_layers,
                                    float *y_out, void *workspace, int64_t workspace_bytes, void *stream) {
+    return forward_prepared_impl(feat, weights, prepared, prepared_bytes, B, n, in_dim, n_layers, 8, y_out, workspace, workspace_bytes,
+                                 stream);
+}
+
+}  // extern "C"
+
+namespace {
+int forward_prepared_impl(const float *feat, const float *weights, const void *prepared, int64_t prepared_bytes, int B, int n,
+                          int in_dim, int n_layers, int n_heads, float *y_out, void *workspace, int64_t workspace_bytes,
+                          void *stream) {
     if (B == 0) return GNNGLS_OK;   // empty batch: nothing to enqueue (data pointers may be NULL)
     if (!feat || !weights || !y_out || !workspace || B < 0 || n < 3 || in_dim < 1 || n_layers < 0)
         return fail(GNNGLS_ERR_ARG, "regret_forward: bad argument");
     if ((in_dim * 128) % 4 != 0) return fail(GNNGLS_ERR_UNSUPPORTED, "regret_forward: in_dim*128 must be a multiple of 4");
-    if (gnngls::gat_rows_lds_bytes(n) > kLdsPerCU)
+    const bool h8 = n_heads == 8;
+    if (h8 && gnngls::gat_rows_lds_bytes(n) > kLdsPerCU)
         return fail(GNNGLS_ERR_UNSUPPORTED, "regret_forward: n=%d needs %zu B of LDS per row tile (> 160 KiB)", n,
                     gnngls::gat_rows_lds_bytes(n));
+    if (!h8 && n > gnngls::heads_max_nodes())
+        return fail(GNNGLS_ERR_UNSUPPORTED, "regret_forward: n=%d exceeds the %d-head attention tile limit (n <= %d; 8 heads: n <= 423)", n,
+                    n_heads, gnngls::heads_max_nodes());
     // prepared == NULL keeps the feed-forward block on the fp32 matrix pipe (as GNNGLS_FFN_FP32=1 does: A/B runs)
     static const bool ffn_fp32 = getenv("GNNGLS_FFN_FP32") && atoi(getenv("GNNGLS_FFN_FP32")) != 0;
     if (prepared && prepared_bytes < gnngls_regret_prepared_bytes(n_layers))
@@ -583,9 +608,9 @@ int gnngls_regret_forward_prepared(const float *feat, const float *weights, cons
     const long N = (long)n * (n - 1) / 2;
     uintptr_t base = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
     int64_t avail = workspace_bytes - (int64_t)(base - (uintptr_t)workspace);
-    long Bc = avail / (N * kBytesPerNode);
+    long Bc = avail / (N * bytes_per_node(n_heads));
     if (Bc < 1) return fail(GNNGLS_ERR_ARG, "regret_forward: workspace too small (%lld B, need >= %lld B)",
-                            (long long)workspace_bytes, (long long)gnngls_regret_forward_workspace_bytes(1, n));
+                            (long long)workspace_bytes, (long long)gnngls_regret_forward_workspace_bytes_heads(1, n, n_heads));
     if (Bc > B) Bc = B;
     hipStream_t st = (hipStream_t)stream;
     const long Mc = Bc * N;
@@ -594,6 +619,7 @@ int gnngls_regret_forward_prepared(const float *feat, const float *weights, cons
     float *part = ft + Mc * 128;
     float *part_ms = part + 2 * Mc * 128;
     float *h2 = part_ms + 2 * Mc * 16;
+    float *hms = h2 + Mc * 128;                          // (16 heads) [2][Mc][32]
     const float *emb_w = weights, *emb_b = weights + 128L * in_dim;
     const float *layers = emb_b + 128;
     const float *dec_w = layers + (long)n_layers * kLayerFloats, *dec_b = dec_w + 128;
@@ -605,7 +631,7 @@ int gnngls_regret_forward_prepared(const float *feat, const float *weights, cons
         // models.py:66; with a prepared image also ft = fc(h) of layer 0 (models.py:23), both straight from the input features
         const bool fused_fc0 = prep && n_layers > 0 && in_dim <= gnngls::embed_fc_max_in_dim();
         static const bool no_rank1 = getenv("GNNGLS_GAT_RANK1") && atoi(getenv("GNNGLS_GAT_RANK1")) == 0;      // (A/B runs)
-        const bool rank1_gat0 = fused_fc0 && in_dim == 1 && n <= 255 && !no_rank1;
+        const bool rank1_gat0 = fused_fc0 && in_dim == 1 && n <= 255 && !no_rank1 && h8;     // (its image holds 8-head coefficients)
         // ... and then the first feed-forward launch forms its input from the one feature and the compact partials (LR0): no embedding
         // pass at all, neither h_0 nor ft_0 nor 128-wide partials of the first layer in memory (GNNGLS_GAT_RANK1=2: keep them, A/B runs)
         static const bool keep_h0 = getenv("GNNGLS_GAT_RANK1") && atoi(getenv("GNNGLS_GAT_RANK1")) == 2;
@@ -630,9 +656,13 @@ int gnngls_regret_forward_prepared(const float *feat, const float *weights, cons
             if (l == 0 && rank1_gat0) {
               ProfScope ps(GNNGLS_PROF_GAT_ROWS_RANK1, st);
               GNNGLS_TRY(gnngls::launch_gat_rows_rank1(feat + b0 * N, prep + (size_t)n_layers * gnngls::ffn_packed_bytes(), bc, n, part, part_ms, st, lr0));
+            } else if (h8) {
+              ProfScope ps(GNNGLS_PROF_GAT_ROWS, st);
+              GNNGLS_TRY(gnngls::launch_gat_rows(ft, attn_l, attn_r, bc, n, part, part_ms, st));
             } else {
               ProfScope ps(GNNGLS_PROF_GAT_ROWS, st);
-              GNNGLS_TRY(gnngls::launch_gat_rows(ft, attn_l, attn_r, bc, n, part, part_ms, st)); }
+              GNNGLS_TRY(gnngls::launch_gat_heads_rows(ft, attn_l, attn_r, bc, n, n_heads, part, part_ms, hms, st));
+              if (n_heads == 16) GNNGLS_TRY(gnngls::launch_gat_heads_merge16(part, hms, part_ms, M, st)); }
             // gat_combine + FFN1 + FFN2 (+ the next layer's fc) in one launch; the hidden layer and x = BN1(h + GAT) never touch HBM
             { ProfScope ps(GNNGLS_PROF_FFN_FUSED, st);
               // (the last layer's launch also applies the decision layer, models.py:69: its output is never stored)
@@ -651,6 +681,9 @@ int gnngls_regret_forward_prepared(const float *feat, const float *weights, cons
 #undef GNNGLS_TRY
     return GNNGLS_OK;
 }
+}  // namespace
+
+extern "C" {
 
 // The one-call form: splits the weights into stream-ordered scratch of its own on every call (gnngls_regret_prepare +
 // gnngls_regret_forward_prepared keep the image across calls: 2 launches per layer and the allocation saved per forward).
@@ -674,6 +707,58 @@ int gnngls_regret_forward(const float *feat, const float *weights, int B, int n,
         if (rc != GNNGLS_OK) return rc;
     }
     return gnngls_regret_forward_prepared(feat, weights, ffn_ws.p, pb, B, n, in_dim, n_layers, y_out, workspace, workspace_bytes, stream);
+}
+
+// ---- head counts other than 8 (embed_dim 128): the same forward with the attention of heads_kernels.hip ----------------------
+int gnngls_model_heads_supported(int n_heads) { return gnngls::heads_supported(n_heads) ? 1 : 0; }
+
+int64_t gnngls_regret_forward_workspace_bytes_heads(int B, int n, int n_heads) {
+    if (!gnngls::heads_supported(n_heads)) return 0;
+    if (n_heads == 8) return gnngls_regret_forward_workspace_bytes(B, n);
+    if (B < 1 || n < 2 || n > 65535) return 0;
+    const long N = (long)n * (n - 1) / 2;
+    return (int64_t)B * N * bytes_per_node(n_heads) + 256;
+}
+
+int gnngls_regret_prepare_heads(const float *weights, int in_dim, int n_layers, int n_heads, void *prepared, int64_t prepared_bytes,
+                                void *stream) {
+    if (!gnngls::heads_supported(n_heads)) return heads_fail("regret_prepare", n_heads);
+    // (the image does not depend on the head count: its rank-1 first-layer coefficients are only read by the 8-head forward)
+    return gnngls_regret_prepare(weights, in_dim, n_layers, prepared, prepared_bytes, stream);
+}
+
+int gnngls_regret_forward_prepared_heads(const float *feat, const float *weights, const void *prepared, int64_t prepared_bytes,
+                                         int B, int n, int in_dim, int n_layers, int n_heads,
+                                         float *y_out, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (!gnngls::heads_supported(n_heads)) return heads_fail("regret_forward", n_heads);
+    return forward_prepared_impl(feat, weights, prepared, prepared_bytes, B, n, in_dim, n_layers, n_heads, y_out, workspace,
+                                 workspace_bytes, stream);
+}
+
+int gnngls_regret_forward_heads(const float *feat, const float *weights, int B, int n, int in_dim, int n_layers, int n_heads,
+                                float *y_out, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (!gnngls::heads_supported(n_heads)) return heads_fail("regret_forward", n_heads);
+    if (n_heads == 8) return gnngls_regret_forward(feat, weights, B, n, in_dim, n_layers, y_out, workspace, workspace_bytes, stream);
+    if (B == 0) return GNNGLS_OK;
+    if (!feat || !weights || !y_out || !workspace || B < 0 || n < 3 || in_dim < 1 || n_layers < 0)
+        return fail(GNNGLS_ERR_ARG, "regret_forward: bad argument");
+    if (n > gnngls::heads_max_nodes())        // (before the scratch image is made)
+        return forward_prepared_impl(feat, weights, nullptr, 0, B, n, in_dim, n_layers, n_heads, y_out, workspace, workspace_bytes, stream);
+    hipStream_t st = (hipStream_t)stream;
+    struct StreamScratch {
+        void *p = nullptr; hipStream_t st;
+        ~StreamScratch() { if (p) (void)hipFreeAsync(p, st); }
+    } ffn_ws;
+    ffn_ws.st = st;
+    static const bool ffn_fp32 = getenv("GNNGLS_FFN_FP32") && atoi(getenv("GNNGLS_FFN_FP32")) != 0;
+    const int64_t pb = gnngls_regret_prepared_bytes(n_layers);
+    if (n_layers > 0 && !ffn_fp32) {
+        hipError_t e = hipMallocAsync(&ffn_ws.p, (size_t)pb, st);
+        if (e != hipSuccess) { ffn_ws.p = nullptr; return hip_fail(e, "regret_forward: scratch alloc"); }
+        const int rc = gnngls_regret_prepare(weights, in_dim, n_layers, ffn_ws.p, pb, stream);
+        if (rc != GNNGLS_OK) return rc;
+    }
+    return forward_prepared_impl(feat, weights, ffn_ws.p, pb, B, n, in_dim, n_layers, n_heads, y_out, workspace, workspace_bytes, stream);
 }
 
 int gnngls_pack_features(const double *D, int B, int n, double scale, double min_, float *feat, void *stream) {
@@ -708,14 +793,14 @@ struct TrainWs {
     float *H1;       // [L][M][128]      h + GATConv(h)
     float *H3;       // [L][M][128]      x + MLP(x), x = BN1(h1)
     float *HID;      // [L][M][512]      ReLU(W1 x + b1); overwritten by its gradient in the backward
-    float *ATT;      // [L][M][16]       softmax statistics (row max, 1/Z) per head
+    float *ATT;      // [L][M][16]       softmax statistics (row max, 1/Z) per head (16 heads: [L][M][32])
     float *BN;       // [L][8][128]      mean1 invstd1 scale1 shift1 mean2 invstd2 scale2 shift2
     float *PART;     // [2][M][128]      attention partials (forward) / P partials (backward)
-    float *PMS;      // [2][M][16]
+    float *PMS;      // [2][M][16]       (16 heads: [2][M][32])
     float *DA, *DB;  // [M][128]         gradient ping-pong
     float *X2;       // [M][128]         BN1 output recomputed in the backward
     float *DFT;      // [M][128]
-    float *DLR;      // [2][M][8]        d el, d er
+    float *DLR;      // [2][M][8]        d el, d er (16 heads: [2][M][16])
     float *WT;       // [2][512*128]     W2^T, W1^T of the layer being differentiated
     float *COEF;     // [3][128] + ones[128] + zeros[512]   BatchNorm backward coefficients, constants
     double *CSP;     // column-sum partials
@@ -723,7 +808,8 @@ struct TrainWs {
     size_t bytes;
 };
 
-TrainWs train_layout(uintptr_t base, long M, int L) {
+// stat_w: softmax statistics per node, 16 (one shift and one sum per 16-column slot, H <= 8) or 32 (16 heads)
+TrainWs train_layout(uintptr_t base, long M, int L, int stat_w = 16) {
     TrainWs w;
     uintptr_t p = (base + 255) & ~(uintptr_t)255;
     auto take = [&](size_t bytes) { uintptr_t q = p; p = (p + bytes + 255) & ~(uintptr_t)255; return q; };
@@ -734,15 +820,15 @@ TrainWs train_layout(uintptr_t base, long M, int L) {
     w.H1 = (float *)take(row * L);
     w.H3 = (float *)take(row * L);
     w.HID = (float *)take(4 * row * L);
-    w.ATT = (float *)take((size_t)M * 16 * sizeof(float) * L);
+    w.ATT = (float *)take((size_t)M * stat_w * sizeof(float) * L);
     w.BN = (float *)take((size_t)L * 8 * 128 * sizeof(float));
     w.PART = (float *)take(2 * row);
-    w.PMS = (float *)take((size_t)2 * M * 16 * sizeof(float));
+    w.PMS = (float *)take((size_t)2 * M * stat_w * sizeof(float));
     w.DA = (float *)take(row);
     w.DB = (float *)take(row);
     w.X2 = (float *)take(row);
     w.DFT = (float *)take(row);
-    w.DLR = (float *)take((size_t)2 * M * 8 * sizeof(float));
+    w.DLR = (float *)take((size_t)2 * M * (stat_w / 2) * sizeof(float));
     w.WT = (float *)take((size_t)2 * 512 * 128 * sizeof(float));
     w.COEF = (float *)take((4 * 128 + 512) * sizeof(float));
     w.CSP = (double *)take((size_t)gnngls::kColsumMaxBlocks * 2 * 512 * sizeof(double));
@@ -763,16 +849,21 @@ void layer_pointers(T *w, T *&fc_w, T *&attn_l, T *&attn_r, T *&bn1_g, T *&bn1_b
 }
 
 int train_check(const char *what, const void *feat, const void *params, const void *io, const void *workspace, int B, int n,
-                int in_dim, int n_layers, int64_t workspace_bytes) {
+                int in_dim, int n_layers, int64_t workspace_bytes, int n_heads = 8) {
+    if (!gnngls::heads_supported(n_heads)) return heads_fail(what, n_heads);
     if (!feat || !params || !io || !workspace || B < 1 || n < 3 || in_dim < 1 || n_layers < 0)
         return fail(GNNGLS_ERR_ARG, "%s: bad argument", what);
     if (n > gnngls::gat_bwd_max_nodes())
         return fail(GNNGLS_ERR_UNSUPPORTED, "%s: n=%d exceeds the attention-backward tile limit (n <= %d)", what, n,
                     gnngls::gat_bwd_max_nodes());
-    if (gnngls::gat_rows_lds_bytes(n) > kLdsPerCU || gnngls::gat_bwd_lds_bytes(n) > kLdsPerCU)
+    if (n_heads == 8 && (gnngls::gat_rows_lds_bytes(n) > kLdsPerCU || gnngls::gat_bwd_lds_bytes(n) > kLdsPerCU))
         return fail(GNNGLS_ERR_UNSUPPORTED, "%s: n=%d needs %zu B of LDS per row tile (> 160 KiB)", what, n,
                     gnngls::gat_bwd_lds_bytes(n));
-    const int64_t need = gnngls_regret_train_workspace_bytes(B, n, n_layers);
+    if (n_heads != 8 && (n > gnngls::heads_max_nodes() || gnngls::gat_heads_rows_lds_bytes(n, n_heads) > kLdsPerCU ||
+                         gnngls::gat_heads_bwd_lds_bytes(n, n_heads) > kLdsPerCU))
+        return fail(GNNGLS_ERR_UNSUPPORTED, "%s: n=%d exceeds the %d-head attention tile limit (n <= %d)", what, n, n_heads,
+                    gnngls::heads_max_nodes());
+    const int64_t need = gnngls_regret_train_workspace_bytes_heads(B, n, n_layers, n_heads);
     if (workspace_bytes < need)
         return fail(GNNGLS_ERR_ARG, "%s: workspace too small (%lld B, need %lld B)", what, (long long)workspace_bytes,
                     (long long)need);
@@ -789,16 +880,31 @@ int64_t gnngls_regret_train_workspace_bytes(int B, int n, int n_layers) {
     return (int64_t)train_layout(0, M, n_layers).bytes + 256;
 }
 
+int64_t gnngls_regret_train_workspace_bytes_heads(int B, int n, int n_layers, int n_heads) {
+    if (!gnngls::heads_supported(n_heads)) return 0;
+    if (B < 1 || n < 2 || n > 65535 || n_layers < 0 || n_layers > 4096) return 0;
+    const long M = (long)B * ((long)n * (n - 1) / 2);
+    return (int64_t)train_layout(0, M, n_layers, n_heads == 16 ? 32 : 16).bytes + 256;
+}
+
 #define GNNGLS_TRY(x) do { e = (x); if (e != hipSuccess) return hip_fail(e, #x); } while (0)
 
 int gnngls_regret_train_forward(const float *feat, const float *params, int B, int n, int in_dim, int n_layers, float bn_eps,
                                 float *y_out, float *bn_batch_stats, void *workspace, int64_t workspace_bytes, void *stream) {
-    int rc = train_check("regret_train_forward", feat, params, y_out, workspace, B, n, in_dim, n_layers, workspace_bytes);
+    return gnngls_regret_train_forward_heads(feat, params, B, n, in_dim, n_layers, 8, bn_eps, y_out, bn_batch_stats, workspace,
+                                             workspace_bytes, stream);
+}
+
+int gnngls_regret_train_forward_heads(const float *feat, const float *params, int B, int n, int in_dim, int n_layers, int n_heads,
+                                      float bn_eps, float *y_out, float *bn_batch_stats, void *workspace, int64_t workspace_bytes,
+                                      void *stream) {
+    int rc = train_check("regret_train_forward", feat, params, y_out, workspace, B, n, in_dim, n_layers, workspace_bytes, n_heads);
     if (rc != GNNGLS_OK) return rc;
     if (!bn_batch_stats && n_layers > 0) return fail(GNNGLS_ERR_ARG, "regret_train_forward: bn_batch_stats is NULL");
     hipStream_t st = (hipStream_t)stream;
     const long N = (long)n * (n - 1) / 2, M = (long)B * N;
-    const TrainWs w = train_layout((uintptr_t)workspace, M, n_layers);
+    const int stat_w = n_heads == 16 ? 32 : 16;
+    const TrainWs w = train_layout((uintptr_t)workspace, M, n_layers, stat_w);
     const float *emb_w = params, *emb_b = params + 128L * in_dim, *layers = emb_b + 128;
     const float *dec_w = layers + (long)n_layers * kLayerFloats, *dec_b = dec_w + 128;
     float *ones = w.COEF + 3 * 128, *zeros = w.COEF + 4 * 128;
@@ -816,15 +922,24 @@ int gnngls_regret_train_forward(const float *feat, const float *params, int B, i
         layer_pointers(layers + (long)l * kLayerFloats, fc_w, attn_l, attn_r, bn1_g, bn1_b, w1, b1, w2, b2, bn2_g, bn2_b);
         const float *h = w.H + row * l;
         float *ft = w.FT + row * l, *g = w.G + row * l, *h1 = w.H1 + row * l, *h3 = w.H3 + row * l;
-        float *att = w.ATT + (size_t)M * 16 * l, *bn = w.BN + (size_t)l * 8 * 128;
+        float *att = w.ATT + (size_t)M * stat_w * l, *bn = w.BN + (size_t)l * 8 * 128;
         float *stats = bn_batch_stats + (size_t)l * 4 * 128;
         int nb = 0;
         { ProfScope ps(GNNGLS_PROF_GEMM_FC, st);
           GNNGLS_TRY(gnngls::launch_gemm(gnngls::GEMM_EPI_STORE, h, fc_w, ft, M, 128, 128, nullptr, nullptr, nullptr, nullptr, st)); }
-        { ProfScope ps(GNNGLS_PROF_GAT_ROWS, st);
-          GNNGLS_TRY(gnngls::launch_gat_rows(ft, attn_l, attn_r, B, n, w.PART, w.PMS, st)); }
-        { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
-          GNNGLS_TRY(gnngls::launch_gat_combine_train(w.PART, w.PMS, h, M, g, h1, att, st)); }          // models.py:12-15
+        if (n_heads == 8) {
+          { ProfScope ps(GNNGLS_PROF_GAT_ROWS, st);
+            GNNGLS_TRY(gnngls::launch_gat_rows(ft, attn_l, attn_r, B, n, w.PART, w.PMS, st)); }
+          { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
+            GNNGLS_TRY(gnngls::launch_gat_combine_train(w.PART, w.PMS, h, M, g, h1, att, st)); }        // models.py:12-15
+        } else {
+          // (H <= 4: slot statistics, gat_combine_train_kernel as for 8 heads; H = 16: per-head statistics and their own merge)
+          { ProfScope ps(GNNGLS_PROF_GAT_ROWS, st);
+            GNNGLS_TRY(gnngls::launch_gat_heads_rows(ft, attn_l, attn_r, B, n, n_heads, w.PART, w.PMS, w.PMS, st)); }
+          { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
+            if (n_heads == 16) GNNGLS_TRY(gnngls::launch_gat_heads_merge16_train(w.PART, w.PMS, h, M, g, h1, att, st));
+            else GNNGLS_TRY(gnngls::launch_gat_combine_train(w.PART, w.PMS, h, M, g, h1, att, st)); }
+        }
         { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);                                                   // models.py:27 (train mode)
           GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_SUM_SQ, h1, nullptr, nullptr, M, 128, 0, w.CSP, &nb, st));
           GNNGLS_TRY(gnngls::launch_bn_stats_finalize(w.CSP, nb, M, bn1_g, bn1_b, bn_eps, bn + 2 * 128, bn + 3 * 128, bn,
@@ -846,12 +961,19 @@ int gnngls_regret_train_forward(const float *feat, const float *params, int B, i
 
 int gnngls_regret_train_backward(const float *feat, const float *params, const float *dy, int B, int n, int in_dim,
                                  int n_layers, float *grads, void *workspace, int64_t workspace_bytes, void *stream) {
-    int rc = train_check("regret_train_backward", feat, params, grads, workspace, B, n, in_dim, n_layers, workspace_bytes);
+    return gnngls_regret_train_backward_heads(feat, params, dy, B, n, in_dim, n_layers, 8, grads, workspace, workspace_bytes, stream);
+}
+
+int gnngls_regret_train_backward_heads(const float *feat, const float *params, const float *dy, int B, int n, int in_dim,
+                                       int n_layers, int n_heads, float *grads, void *workspace, int64_t workspace_bytes,
+                                       void *stream) {
+    int rc = train_check("regret_train_backward", feat, params, grads, workspace, B, n, in_dim, n_layers, workspace_bytes, n_heads);
     if (rc != GNNGLS_OK) return rc;
     if (!dy) return fail(GNNGLS_ERR_ARG, "regret_train_backward: dy is NULL");
     hipStream_t st = (hipStream_t)stream;
     const long N = (long)n * (n - 1) / 2, M = (long)B * N;
-    const TrainWs w = train_layout((uintptr_t)workspace, M, n_layers);
+    const int stat_w = n_heads == 16 ? 32 : 16;
+    const TrainWs w = train_layout((uintptr_t)workspace, M, n_layers, stat_w);
     const float *layers = params + 128L * in_dim + 128;
     const float *dec_w = layers + (long)n_layers * kLayerFloats;
     float *g_emb_w = grads, *g_emb_b = grads + 128L * in_dim, *g_layers = g_emb_b + 128;
@@ -874,7 +996,7 @@ int gnngls_regret_train_backward(const float *feat, const float *params, const f
         layer_pointers(g_layers + (long)l * kLayerFloats, d_fc_w, d_attn_l, d_attn_r, d_bn1_g, d_bn1_b, d_w1, d_b1, d_w2,
                        d_b2, d_bn2_g, d_bn2_b);
         const float *h = w.H + row * l, *ft = w.FT + row * l, *g = w.G + row * l, *h1 = w.H1 + row * l, *h3 = w.H3 + row * l;
-        const float *att = w.ATT + (size_t)M * 16 * l, *bn = w.BN + (size_t)l * 8 * 128;
+        const float *att = w.ATT + (size_t)M * stat_w * l, *bn = w.BN + (size_t)l * 8 * 128;
         // BatchNorm 2 backward (models.py:35): DA = d(layer output) -> DB = d h3
         { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);
           GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_SUM_PROD, w.DA, h3, nullptr, M, 128, 0, w.CSP, &nb, st));
@@ -899,13 +1021,25 @@ int gnngls_regret_train_backward(const float *feat, const float *params, const f
         { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
           GNNGLS_TRY(gnngls::launch_bn_bwd_apply(w.DA, h1, bn, w.COEF, w.DB, M, st)); }
         // GATConv backward (models.py:23)
-        { ProfScope ps(GNNGLS_PROF_TRAIN_GAT_BWD, st);
-          GNNGLS_TRY(gnngls::launch_gat_bwd_rows(ft, w.DB, g, att, attn_l, attn_r, B, n, w.PART, w.PMS, st)); }
-        { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
-          GNNGLS_TRY(gnngls::launch_gat_bwd_combine(w.PART, w.PMS, attn_l, attn_r, M, w.DFT, w.DLR, w.DLR + (size_t)M * 8, st)); }
-        { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);
-          GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_HEADSCALE, ft, w.DLR, w.DLR + (size_t)M * 8, M, 128, 0, w.CSP, &nb, st));
-          GNNGLS_TRY(gnngls::launch_colsum_store(w.CSP, nb, 128, 1, d_attn_l, d_attn_r, st)); }
+        if (n_heads == 16) {        // per-head d el / d er: combine and attention-vector sums of their own
+          { ProfScope ps(GNNGLS_PROF_TRAIN_GAT_BWD, st);
+            GNNGLS_TRY(gnngls::launch_gat_heads_bwd_rows(ft, w.DB, g, att, attn_l, attn_r, B, n, n_heads, w.PART, w.PMS, st)); }
+          { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
+            GNNGLS_TRY(gnngls::launch_gat_heads_bwd_combine16(w.PART, w.PMS, attn_l, attn_r, M, w.DFT, w.DLR, w.DLR + (size_t)M * 16, st)); }
+          { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);
+            nb = gnngls::colsum_blocks(M, 128);
+            GNNGLS_TRY(gnngls::launch_colsum_heads16(ft, w.DLR, w.DLR + (size_t)M * 16, M, w.CSP, nb, st));
+            GNNGLS_TRY(gnngls::launch_colsum_store(w.CSP, nb, 128, 1, d_attn_l, d_attn_r, st)); }
+        } else {
+          { ProfScope ps(GNNGLS_PROF_TRAIN_GAT_BWD, st);
+            if (n_heads == 8) GNNGLS_TRY(gnngls::launch_gat_bwd_rows(ft, w.DB, g, att, attn_l, attn_r, B, n, w.PART, w.PMS, st));
+            else GNNGLS_TRY(gnngls::launch_gat_heads_bwd_rows(ft, w.DB, g, att, attn_l, attn_r, B, n, n_heads, w.PART, w.PMS, st)); }
+          { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
+            GNNGLS_TRY(gnngls::launch_gat_bwd_combine(w.PART, w.PMS, attn_l, attn_r, M, w.DFT, w.DLR, w.DLR + (size_t)M * 8, st)); }
+          { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);
+            GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_HEADSCALE, ft, w.DLR, w.DLR + (size_t)M * 8, M, 128, 0, w.CSP, &nb, st));
+            GNNGLS_TRY(gnngls::launch_colsum_store(w.CSP, nb, 128, 1, d_attn_l, d_attn_r, st)); }
+        }
         { ProfScope ps(GNNGLS_PROF_TRAIN_GEMM_TN, st);
           GNNGLS_TRY(gnngls::launch_gemm_tn(w.DFT, h, M, 128, 128, w.TNP, d_fc_w, nullptr, st)); }
         { ProfScope ps(GNNGLS_PROF_TRAIN_GEMM_BWD, st);      // d h = d ft * Wfc + d h1 (skip, models.py:15)

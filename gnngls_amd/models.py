@@ -25,6 +25,7 @@ from . import _lib
 
 EMBED_DIM = 128
 N_HEADS = 8
+SUPPORTED_HEADS = (1, 2, 4, 8, 16)      # head counts of the HIP kernels at embed_dim 128 (include/gnngls_hip.h, *_heads entries)
 HIDDEN_DIM = 512
 
 
@@ -135,10 +136,10 @@ class EdgePropertyPredictionModel(nn.Module):
 
     # -- weight image -----------------------------------------------------------------------------
     def _check_supported(self):
-        if self.embed_dim != EMBED_DIM or self.n_heads != N_HEADS or self.out_dim != 1:
+        if self.embed_dim != EMBED_DIM or self.n_heads not in SUPPORTED_HEADS or self.out_dim != 1:
             raise NotImplementedError(
-                "the HIP forward is specialised to the reference architecture (embed_dim=128, n_heads=8, "
-                f"out_dim=1; got embed_dim={self.embed_dim}, n_heads={self.n_heads}, out_dim={self.out_dim})")
+                "the HIP forward is specialised to embed_dim=128, n_heads in {1, 2, 4, 8, 16} and out_dim=1 "
+                f"(got embed_dim={self.embed_dim}, n_heads={self.n_heads}, out_dim={self.out_dim})")
 
     @staticmethod
     def _bn_affine(bn):
@@ -231,20 +232,28 @@ class _TrainStep(torch.autograd.Function):
         assert image.numel() == L.gnngls_model_packed_floats(model.in_dim, n_layers)
         N = n * (n - 1) // 2
         # the workspace holds the activations the backward needs: one per forward call, owned by the autograd node
-        ws = torch.empty(int(L.gnngls_regret_train_workspace_bytes(B, n, n_layers)), dtype=torch.uint8, device=dev)
+        H = model.n_heads
+        ws_bytes = (L.gnngls_regret_train_workspace_bytes(B, n, n_layers) if H == N_HEADS
+                    else L.gnngls_regret_train_workspace_bytes_heads(B, n, n_layers, H))
+        ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
         y = torch.empty((B * N, 1), dtype=torch.float32, device=dev)
         stats = torch.empty((n_layers, 2, 2, EMBED_DIM), dtype=torch.float32, device=dev)
         bns = model.batch_norms()
         eps = bns[0].eps if bns else 1e-5
-        _lib.check(L.gnngls_regret_train_forward(_lib.ptr(x), _lib.ptr(image), B, n, model.in_dim, n_layers, eps,
-                                                 _lib.ptr(y), _lib.ptr(stats), _lib.ptr(ws), ctypes.c_int64(ws.numel()),
-                                                 _lib.current_stream()), "regret_train_forward")
+        if H == N_HEADS:
+            rc = L.gnngls_regret_train_forward(_lib.ptr(x), _lib.ptr(image), B, n, model.in_dim, n_layers, eps, _lib.ptr(y),
+                                               _lib.ptr(stats), _lib.ptr(ws), ctypes.c_int64(ws.numel()), _lib.current_stream())
+        else:
+            rc = L.gnngls_regret_train_forward_heads(_lib.ptr(x), _lib.ptr(image), B, n, model.in_dim, n_layers, H, eps,
+                                                     _lib.ptr(y), _lib.ptr(stats), _lib.ptr(ws), ctypes.c_int64(ws.numel()),
+                                                     _lib.current_stream())
+        _lib.check(rc, "regret_train_forward")
         # GATConv bias (DGL >= 0.7): h1 = h + GATConv(h) + bias feeds BatchNorm-1 only; in training mode its batch mean
         # takes the constant up (variance, prediction and every other gradient unchanged), so the kernels run without it
         for (k, _), bias in zip(model.gat_biases(), biases):
             stats[k, 0, 0] += bias.detach().reshape(-1)
         _update_running_stats(bns, stats.reshape(-1, 2, EMBED_DIM))
-        ctx.model_dims = (B, n, model.in_dim, n_layers)
+        ctx.model_dims = (B, n, model.in_dim, n_layers, H)
         ctx.shapes = [p.shape for p in params]
         ctx.bias_shapes = [b.shape for b in biases]
         ctx.save_for_backward(x, image)
@@ -258,12 +267,18 @@ class _TrainStep(torch.autograd.Function):
             raise RuntimeError("the activations of this training forward were consumed by its first backward "
                                "(the hidden activations are overwritten in place): retain_graph is not supported")
         x, image = ctx.saved_tensors
-        B, n, in_dim, n_layers = ctx.model_dims
+        B, n, in_dim, n_layers, H = ctx.model_dims
         grads = torch.empty_like(image)
         dy = dy.contiguous().float()
-        _lib.check(L.gnngls_regret_train_backward(_lib.ptr(x), _lib.ptr(image), _lib.ptr(dy), B, n, in_dim, n_layers,
-                                                  _lib.ptr(grads), _lib.ptr(ctx.ws), ctypes.c_int64(ctx.ws.numel()),
-                                                  _lib.current_stream()), "regret_train_backward")
+        if H == N_HEADS:
+            rc = L.gnngls_regret_train_backward(_lib.ptr(x), _lib.ptr(image), _lib.ptr(dy), B, n, in_dim, n_layers,
+                                                _lib.ptr(grads), _lib.ptr(ctx.ws), ctypes.c_int64(ctx.ws.numel()),
+                                                _lib.current_stream())
+        else:
+            rc = L.gnngls_regret_train_backward_heads(_lib.ptr(x), _lib.ptr(image), _lib.ptr(dy), B, n, in_dim, n_layers, H,
+                                                      _lib.ptr(grads), _lib.ptr(ctx.ws), ctypes.c_int64(ctx.ws.numel()),
+                                                      _lib.current_stream())
+        _lib.check(rc, "regret_train_backward")
         ctx.ws = None
         out, off = [], 0
         for shape in ctx.shapes:
@@ -301,6 +316,9 @@ def regret_forward(model, feat, B, n, max_workspace_bytes=48 << 30):
     dev = feat.device
     version = model._state_version()
     n_layers = len(model.message_passing_layers)
+    H = model.n_heads
+    if H != N_HEADS:
+        return _regret_forward_heads(model, feat, B, n, H, dev, version, n_layers, max_workspace_bytes)
     if model._packed is None or model._packed.device != dev or getattr(model, "_packed_version", None) != version:
         model._packed = model.pack_weights(dev)
         model._packed_version = version
@@ -329,6 +347,32 @@ def regret_forward(model, feat, B, n, max_workspace_bytes=48 << 30):
                                                 ctypes.c_int64(model._prepared.numel()), B, n, model.in_dim, n_layers,
                                                 _lib.ptr(y), _lib.ptr(ws), ctypes.c_int64(ws.numel()), _lib.current_stream()),
                "regret_forward")
+    return y
+
+
+def _regret_forward_heads(model, feat, B, n, H, dev, version, n_layers, max_workspace_bytes):
+    """regret_forward for n_heads != 8 (the *_heads entries of include/gnngls_hip.h); the prepared image is the same for every
+    head count of the same weights."""
+    L = _lib.load()
+    if model._packed is None or model._packed.device != dev or getattr(model, "_packed_version", None) != version:
+        model._packed = model.pack_weights(dev)
+        model._packed_version = version
+        model._prepared = torch.empty(int(L.gnngls_regret_prepared_bytes(n_layers)), dtype=torch.uint8, device=dev)
+        _lib.check(L.gnngls_regret_prepare_heads(_lib.ptr(model._packed), model.in_dim, n_layers, H, _lib.ptr(model._prepared),
+                                                 ctypes.c_int64(model._prepared.numel()), _lib.current_stream()), "regret_prepare")
+    N = n * (n - 1) // 2
+    need = int(L.gnngls_regret_forward_workspace_bytes_heads(B, n, H))
+    ws_bytes = min(need, max(int(L.gnngls_regret_forward_workspace_bytes_heads(1, n, H)), max_workspace_bytes))
+    ws = model._workspace
+    if ws is None or ws.device != dev or ws.numel() < ws_bytes:
+        model._workspace = None
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        model._workspace = ws
+    y = torch.empty((B, N), dtype=torch.float32, device=dev)
+    _lib.check(L.gnngls_regret_forward_prepared_heads(_lib.ptr(feat), _lib.ptr(model._packed), _lib.ptr(model._prepared),
+                                                      ctypes.c_int64(model._prepared.numel()), B, n, model.in_dim, n_layers, H,
+                                                      _lib.ptr(y), _lib.ptr(ws), ctypes.c_int64(ws.numel()),
+                                                      _lib.current_stream()), "regret_forward")
     return y
 
 

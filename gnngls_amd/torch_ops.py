@@ -7,7 +7,8 @@ functions (fake/meta kernels) are registered so the ops can be traced and used u
 the current HIP stream, take caller-owned contiguous tensors and retain nothing.
 
     regret_forward(feat[B,N] f32, packed_weights f32, n, heads=8, head_dim=16, hidden=512, layers) -> [B,N] f32
-        EdgePropertyPredictionModel.forward (models.py:44-70); packed_weights = model.pack_weights(device)
+        EdgePropertyPredictionModel.forward (models.py:44-70); packed_weights = model.pack_weights(device);
+        (heads, head_dim) in {(1, 128), (2, 64), (4, 32), (8, 16), (16, 8)} (embed_dim 128)
     two_opt_delta_all(tour[B,n+1] i32, D[B,n,n] f64) -> [B,n+1,n+1] f64          operators.py:14-29
     relocate_delta_all(tour, D) -> [B,n+1,n+1] f64                                operators.py:83-103
     local_search(tour, cost[B] f64, D, first_improvement) -> (tour, cost, n_moves[B] i32)      algorithms.py:111-132
@@ -34,9 +35,9 @@ _workspaces = {}      # device index -> uint8 scratch tensor for the forward (gr
 
 
 def _regret_forward(feat, packed_weights, n, heads, head_dim, hidden, layers):
-    if (heads, head_dim, hidden) != (8, 16, 512):
-        raise NotImplementedError("gnngls::regret_forward is specialised to the reference architecture "
-                                  "(8 heads x 16, hidden 512: models.py:23,60)")
+    if heads not in (1, 2, 4, 8, 16) or heads * head_dim != 128 or hidden != 512:
+        raise NotImplementedError("gnngls::regret_forward is specialised to embed_dim 128 = heads x head_dim with heads in "
+                                  f"{{1, 2, 4, 8, 16}} and hidden 512 (models.py:23,60; got {heads} x {head_dim}, {hidden})")
     L = _lib.load()
     N = n * (n - 1) // 2
     feat = feat.contiguous().float()
@@ -45,16 +46,25 @@ def _regret_forward(feat, packed_weights, n, heads, head_dim, hidden, layers):
     expect = int(L.gnngls_model_packed_floats(in_dim, layers))
     if packed_weights.numel() != expect or packed_weights.dtype != torch.float32:
         raise ValueError(f"packed_weights must hold {expect} fp32 values for in_dim={in_dim}, layers={layers}")
-    need = int(L.gnngls_regret_forward_workspace_bytes(B, n))
-    ws_bytes = min(need, max(int(L.gnngls_regret_forward_workspace_bytes(1, n)), 48 << 30))
+    if heads == 8:
+        need = int(L.gnngls_regret_forward_workspace_bytes(B, n))
+        ws_bytes = min(need, max(int(L.gnngls_regret_forward_workspace_bytes(1, n)), 48 << 30))
+    else:
+        need = int(L.gnngls_regret_forward_workspace_bytes_heads(B, n, heads))
+        ws_bytes = min(need, max(int(L.gnngls_regret_forward_workspace_bytes_heads(1, n, heads)), 48 << 30))
     key = feat.device.index
     ws = _workspaces.get(key)
     if ws is None or ws.numel() < ws_bytes:
         _workspaces[key] = None
         ws = _workspaces[key] = torch.empty(ws_bytes, dtype=torch.uint8, device=feat.device)
     y = torch.empty((B, N), dtype=torch.float32, device=feat.device)
-    _lib.check(L.gnngls_regret_forward(_lib.ptr(feat), _lib.ptr(packed_weights.contiguous()), B, n, in_dim, layers, _lib.ptr(y),
-                                       _lib.ptr(ws), ctypes.c_int64(ws.numel()), _lib.current_stream()), "regret_forward")
+    if heads == 8:
+        _lib.check(L.gnngls_regret_forward(_lib.ptr(feat), _lib.ptr(packed_weights.contiguous()), B, n, in_dim, layers, _lib.ptr(y),
+                                           _lib.ptr(ws), ctypes.c_int64(ws.numel()), _lib.current_stream()), "regret_forward")
+    else:
+        _lib.check(L.gnngls_regret_forward_heads(_lib.ptr(feat), _lib.ptr(packed_weights.contiguous()), B, n, in_dim, layers, heads,
+                                                 _lib.ptr(y), _lib.ptr(ws), ctypes.c_int64(ws.numel()), _lib.current_stream()),
+                   "regret_forward")
     return y
 
 

@@ -244,6 +244,34 @@ int gnngls_regret_train_forward(const float *feat, const float *params, int B, i
 int gnngls_regret_train_backward(const float *feat, const float *params, const float *dy, int B, int n, int in_dim,
                                  int n_layers, float *grads, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- other head counts: GATConv(128, 128 / n_heads, n_heads) (models.py:23) with n_heads layers (models.py:59-61) ----------
+ * The reference builds any head count that divides embed_dim (scripts/train.py:76 --n_heads); with embed_dim 128 these entries
+ * take n_heads in {1, 2, 4, 8, 16} (F = 128 / n_heads features per head).  The weight images keep their size and layout for every
+ * head count (attn_l / attn_r hold the (1, n_heads, F) parameters flattened head-major: 128 floats), so
+ * gnngls_model_packed_floats and gnngls_regret_prepared_bytes hold as they are.  Each entry below is the entry without the
+ * _heads suffix with `n_heads` next to n_layers; n_heads = 8 IS that entry (same kernels, same results).  Any other n_heads
+ * returns GNNGLS_ERR_UNSUPPORTED before any device work.  Limits for n_heads != 8: 3 <= n <= 257 in the forward and the
+ * training step (the 8-head forward goes to n = 423); a larger n returns GNNGLS_ERR_UNSUPPORTED.
+ * The prepared image does not depend on the head count (its rank-1 first-layer coefficients are read by the 8-head forward
+ * only), so an image made by either prepare entry is valid for every head count of the same weights. */
+int gnngls_model_heads_supported(int n_heads);                          /* 1 for n_heads in {1, 2, 4, 8, 16}, else 0 */
+int64_t gnngls_regret_forward_workspace_bytes_heads(int B, int n, int n_heads);         /* 16 heads: 256 B per node more */
+int gnngls_regret_forward_heads(const float *feat, const float *weights, int B, int n, int in_dim, int n_layers, int n_heads,
+                                float *y_out, void *workspace, int64_t workspace_bytes, void *stream);
+int gnngls_regret_prepare_heads(const float *weights, int in_dim, int n_layers, int n_heads, void *prepared, int64_t prepared_bytes,
+                                void *stream);
+int gnngls_regret_forward_prepared_heads(const float *feat, const float *weights, const void *prepared, int64_t prepared_bytes,
+                                         int B, int n, int in_dim, int n_layers, int n_heads,
+                                         float *y_out, void *workspace, int64_t workspace_bytes, void *stream);
+/* training step (scripts/train.py:20-32); the workspace of 16 heads keeps per-head softmax statistics (2 x 16 per node) */
+int64_t gnngls_regret_train_workspace_bytes_heads(int B, int n, int n_layers, int n_heads);
+int gnngls_regret_train_forward_heads(const float *feat, const float *params, int B, int n, int in_dim, int n_layers, int n_heads,
+                                      float bn_eps, float *y_out, float *bn_batch_stats, void *workspace, int64_t workspace_bytes,
+                                      void *stream);
+int gnngls_regret_train_backward_heads(const float *feat, const float *params, const float *dy, int B, int n, int in_dim,
+                                       int n_layers, int n_heads, float *grads, void *workspace, int64_t workspace_bytes,
+                                       void *stream);
+
 /* get_scaled_features (datasets.py:73-95) for features=[weight] (datasets.py:14-20):
  * feat[b, rank(i<j)] = MinMaxScaler.transform(float32(D[b,i,j])) with sklearn's fp32 arithmetic
  * (x*scale_ rounded to fp32, + min_ rounded to fp32). */

@@ -37,6 +37,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--n_heads", type=int, default=8, help="attention heads (1, 2, 4, 8 or 16) and layers of the model")
     ap.add_argument("--no-optimizer", action="store_true")
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--graph", action="store_true",
@@ -45,7 +46,7 @@ def main():
     n, B = args.n, args.batch
     N = n * (n - 1) // 2
     torch.manual_seed(0)
-    model = models.EdgePropertyPredictionModel(1, 128, 1, 3, n_heads=8).cuda().train()
+    model = models.EdgePropertyPredictionModel(1, 128, 1, 3, n_heads=args.n_heads).cuda().train()
     opt = torch.optim.Adam(model.parameters(), lr=1e-3, capturable=args.graph)   # train.py:104
     crit = torch.nn.MSELoss()                                                   # train.py:108
     rng = np.random.default_rng(0)
@@ -87,16 +88,17 @@ def main():
     dt = time.time() - t0
     prof = _lib.profile_collect()
     _lib.profile_enable(False)
-    fwd, bwd = flops_per_instance(n)
+    H = args.n_heads                                     # (= the layer count, models.py:59-61)
+    fwd, bwd = flops_per_instance(n, H)
     ms = dt / args.steps * 1e3
     kern = {k: {"ms_per_step": v[0] / args.steps, "launches_per_step": v[1] / args.steps} for k, v in prof.items() if v[1]}
-    # algorithmic FLOP per step of the MFMA kernel classes (8 layers, M = B*N rows) -> achieved TFLOP/s vs the 157.3 dense
+    # algorithmic FLOP per step of the MFMA kernel classes (H layers, M = B*N rows) -> achieved TFLOP/s vs the 157.3 dense
     # fp32 MFMA peak of MI355X
     M, E = B * N, B * N * 2 * (n - 2)
-    algo = {"ffn_fused": 8 * 4 * M * 128 * 512, "gemm_fc": 8 * 2 * M * 128 * 128,
-            "train_gemm_bwd": 8 * (4 * M * 128 * 512 + 2 * M * 128 * 128),
-            "train_gemm_tn": 8 * (4 * M * 128 * 512 + 2 * M * 128 * 128),
-            "gat_rows": 8 * E * 304, "train_gat_bwd": 8 * E * 608}
+    algo = {"ffn_fused": H * 4 * M * 128 * 512, "gemm_fc": H * 2 * M * 128 * 128,
+            "train_gemm_bwd": H * (4 * M * 128 * 512 + 2 * M * 128 * 128),
+            "train_gemm_tn": H * (4 * M * 128 * 512 + 2 * M * 128 * 128),
+            "gat_rows": H * E * 304, "train_gat_bwd": H * E * 608}
     for k, f in algo.items():
         if k in kern:
             kern[k]["tflops"] = f / (kern[k]["ms_per_step"] * 1e-3) / 1e12
@@ -112,18 +114,18 @@ def main():
            "model_tflops": (fwd + bwd) * B / (ms * 1e-3) / 1e12,
            "kernel_ms_per_step": sum(v["ms_per_step"] for v in kern.values() if "ms_per_step" in v), "roofline": roofline,
            "kernels": kern,
-           "workspace_gib": _lib.load().gnngls_regret_train_workspace_bytes(B, n, 8) / 2 ** 30}
+           "n_heads": H, "workspace_gib": _lib.load().gnngls_regret_train_workspace_bytes_heads(B, n, H, H) / 2 ** 30}
     if not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(n)
+        out["cpu_baseline"] = cpu_baseline(n, H)
     print(json.dumps(out))
 
 
-def cpu_baseline(n):
+def cpu_baseline(n, n_heads=8):
     """The CPU oracle (plain PyTorch fp32 autograd of the reference's graph, oracle/model_oracle.py) on a bounded sample:
     one forward+backward+Adam step on a batch of ONE instance of the same size, all host cores."""
     from oracle import model_oracle as mo
     torch.manual_seed(0)
-    model = mo.EdgeRegretModelOracle(1, 128, 1, 3, n_heads=8).train()
+    model = mo.EdgeRegretModelOracle(1, 128, 1, 3, n_heads=n_heads).train()
     opt = torch.optim.Adam(model.parameters(), lr=1e-3)
     N = n * (n - 1) // 2
     G = mo.batch_line_graphs(n, 1)

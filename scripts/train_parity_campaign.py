@@ -4,7 +4,9 @@ tensor of the HIP path and of the fp32 CPU oracle against the fp64 oracle.  Prin
 whole gradient and the worst per-tensor relative L2 / max errors of both, and checks the same bounds as
 tests/test_train_gpu.py.
 
-    python scripts/train_parity_campaign.py [--cases 20] [--seed 1] [--max_n 40]
+    python scripts/train_parity_campaign.py [--cases 20] [--seed 1] [--max_n 40] [--n_heads 8]
+
+--n_heads H (1, 2, 4 or 16): the model of H heads x 128/H features and H layers (tests/test_heads_gpu.py::make_models).
 """
 import argparse
 import copy
@@ -19,6 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import test_train_gpu as T  # noqa: E402
+import test_heads_gpu as TH  # noqa: E402
 from oracle import model_oracle as mo  # noqa: E402
 
 
@@ -27,12 +30,16 @@ def main():
     ap.add_argument("--cases", type=int, default=20)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--max_n", type=int, default=40)
+    ap.add_argument("--n_heads", type=int, default=8)
     args = ap.parse_args()
     rng = np.random.default_rng(args.seed)
     t0, failed, stats = time.time(), 0, []
     for _ in range(args.cases):
         n, B = int(rng.integers(3, args.max_n + 1)), int(rng.integers(1, 5))
-        model, oracle = T.make_models(4321, 77)
+        if args.n_heads == 8:
+            model, oracle = T.make_models(4321, 77)
+        else:
+            model, oracle, _ = TH.make_models(args.n_heads, seed=4321, sd_seed=77)
         oracle64 = copy.deepcopy(oracle).double()
         N = n * (n - 1) // 2
         drng = np.random.default_rng(int(rng.integers(1 << 30)))
@@ -51,7 +58,7 @@ def main():
               f"fp32 {m['worst_max_32']:.1e} | median max-rel hip {m['median_max_hip']:.1e} fp32 {m['median_max_32']:.1e}")
     a = np.array(stats)
     med, p90 = np.median(a, axis=0), np.quantile(a, 0.9, axis=0)
-    print(f"{args.cases} random (n, batch) training steps, {time.time() - t0:.0f} s; whole-gradient relative L2 error: median hip "
+    print(f"n_heads={args.n_heads}: {args.cases} random (n, batch) training steps, {time.time() - t0:.0f} s; whole-gradient relative L2 error: median hip "
           f"{med[0]:.1e} / fp32 oracle {med[1]:.1e}, 90th percentile hip {p90[0]:.1e} / fp32 oracle {p90[1]:.1e}; worst entry error "
           f"(of max|g|): median hip {med[2]:.1e} / fp32 oracle {med[3]:.1e}; {failed} cases outside the per-case bounds "
           "(a kink flip on one side only)")
