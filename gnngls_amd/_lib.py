@@ -28,6 +28,8 @@ SIGNATURES = {
     "gnngls_best_move": [_vp, _vp, _int, _int, _int, _vp, _int, _vp, _vp, _vp, _vp],
     "gnngls_tour_cost": [_vp, _vp, _int, _int, _vp, _vp],
     "gnngls_nearest_neighbor": [_vp, _int, _int, _int, _vp, _vp],
+    "gnngls_insertion": [_vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp],
+    "gnngls_cheapest_insertion": [_vp, _int, _vp, _vp, _int, _int, _vp, _vp, _vp],
     "gnngls_gls_run": [_vp, _vp, _int, _int, _int, _vp, _vp, _int, _int, _int, _i64, _f64, _f64,
                        _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp],
     "gnngls_model_packed_floats": [_int, _int],
@@ -65,7 +67,7 @@ SIGNATURES = {
 
 PROF_KINDS = ["pack_features", "embed", "gemm_fc", "gat_rows", "gat_rows_rank1", "gemm_ffn1(unused)", "gemm_ffn2(unused)",
               "decision", "unpack_regret", "nearest_neighbor", "tour_cost", "gls", "ffn_fused",
-              "train_colsum", "train_elementwise", "train_gemm_bwd", "train_gemm_tn", "train_gat_bwd"]
+              "train_colsum", "train_elementwise", "train_gemm_bwd", "train_gemm_tn", "train_gat_bwd", "insertion"]
 
 
 def profile_enable(on=True):
@@ -92,6 +94,8 @@ _ABI4 = ("gnngls_regret_prepared_bytes", "gnngls_regret_prepare", "gnngls_regret
 _HEADS = ("gnngls_model_heads_supported", "gnngls_regret_forward_workspace_bytes_heads", "gnngls_regret_forward_heads",
           "gnngls_regret_prepare_heads", "gnngls_regret_forward_prepared_heads", "gnngls_regret_train_workspace_bytes_heads",
           "gnngls_regret_train_forward_heads", "gnngls_regret_train_backward_heads")
+# the insertion tour constructors (an older build named by GNNGLS_HIP_SO lacks them; ops.insertion then raises)
+_CONSTRUCTORS = ("gnngls_insertion", "gnngls_cheapest_insertion")
 _lib = None
 
 
@@ -114,7 +118,7 @@ def load():
         import torch  # noqa: F401
         L = ctypes.CDLL(SO)
         for name, argtypes in SIGNATURES.items():
-            if (name in _ABI4 or name in _HEADS) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
+            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
                 continue              # an older build of the library named by GNNGLS_HIP_SO (same-box A/B of kernel variants)
             f = getattr(L, name)      # AttributeError if the symbol is missing
             f.argtypes = argtypes

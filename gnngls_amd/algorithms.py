@@ -1,9 +1,9 @@
-"""Mirror of the hot-path functions of gnngls/algorithms.py (reference algorithms.py:9-18,111-195):
-`nearest_neighbor`, `local_search`, `guided_local_search` with the reference's signatures, return
-values and side effects, executed by the persistent HIP search kernel.
+"""Mirror of gnngls/algorithms.py (reference algorithms.py:9-18,67-195): `nearest_neighbor`, `cheapest_insertion`,
+`insertion`, `local_search`, `guided_local_search` with the reference's signatures, return values and side
+effects, executed by the HIP kernels (the persistent search kernel, the one-launch insertion constructor).
 
-The alternative tour constructors of the reference (algorithms.py:21-108) are never called by any
-script and are out of scope (SURVEY.md C3').
+The probabilistic constructors (algorithms.py:21-64) stay out of scope: their result depends on NumPy's internal
+pairwise summation (`np.sum(p)`) and on draws that interleave with the state of the walk.
 """
 import time
 import warnings
@@ -42,6 +42,25 @@ def nearest_neighbor(G, depot, weight="weight"):
     """algorithms.py:9-18 (greedy on G.edges[(i,j)][weight]; ties -> first neighbour = lowest id)."""
     W = ops.as_dev(_attr_matrix(G, weight)[None], torch.float64)
     return ops.nearest_neighbor(W, depot)[0].tolist()
+
+
+def cheapest_insertion(G, sub_tour, n, weight="weight"):
+    """algorithms.py:67-79: `n` is the node to insert; the first position with the strictly smallest tour_cost wins.
+    A sub-tour of fewer than two entries has no position (the reference's loop is empty): None."""
+    if len(sub_tour) < 2:
+        return None
+    W = ops.as_dev(_attr_matrix(G, weight)[None], torch.float64)
+    tour, _ = ops.cheapest_insertion(ops.as_dev(np.asarray(sub_tour, dtype=np.int32)[None], torch.int32),
+                                     ops.as_dev(np.asarray([n], dtype=np.int32), torch.int32), W)
+    return tour[0].tolist()
+
+
+def insertion(G, depot, mode="farthest", weight="weight"):
+    """algorithms.py:82-108.  mode 'random' draws its nodes with the reference's np.random.choice calls on the host
+    (ops.random_order), so NumPy's global stream ends where the reference leaves it."""
+    assert mode in ['random', 'nearest', 'farthest'], f'Unknown mode: {mode}'
+    W = ops.as_dev(_attr_matrix(G, weight)[None], torch.float64)
+    return ops.insertion(W, depot, mode)[0].tolist()
 
 
 def _check_status(r, what):

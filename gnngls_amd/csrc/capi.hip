@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/gnngls_hip.h"
+#include "constructors_kernels.h"
 #include "gls_kernels.h"
 #include "heads_kernels.h"
 #include "labels_kernels.h"
@@ -284,6 +285,42 @@ int gnngls_nearest_neighbor(const double *W, int B, int n, int depot, int32_t *t
     ProfScope ps(GNNGLS_PROF_NEAREST_NEIGHBOR, (hipStream_t)stream);
     hipError_t e = gnngls::launch_nearest_neighbor(W, B, n, depot, tour_out, (hipStream_t)stream);
     return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "nearest_neighbor");
+}
+
+static_assert(GNNGLS_INSERTION_MAX_N == gnngls::kInsertionMaxN, "include/gnngls_hip.h and constructors_kernels.h disagree");
+
+int gnngls_insertion(const double *W, int B, int n, int depot, int mode, const int32_t *order, int32_t *tour_out,
+                     int32_t *status, void *stream) {
+    if (B == 0) return GNNGLS_OK;
+    if (!W || !tour_out) return fail(GNNGLS_ERR_ARG, "insertion: NULL pointer (W, tour_out)");
+    if (B < 0) return fail(GNNGLS_ERR_ARG, "insertion: B=%d must be >= 0", B);
+    if (n < 1) return fail(GNNGLS_ERR_ARG, "insertion: n=%d must be >= 1", n);
+    if (depot < 0 || depot >= n) return fail(GNNGLS_ERR_ARG, "insertion: depot=%d out of range (0..%d)", depot, n - 1);
+    if (mode != GNNGLS_INSERT_NEAREST && mode != GNNGLS_INSERT_FARTHEST && mode != GNNGLS_INSERT_GIVEN_ORDER)
+        return fail(GNNGLS_ERR_ARG, "insertion: unknown mode %d", mode);
+    if (mode == GNNGLS_INSERT_GIVEN_ORDER && (!status || (!order && n > 1)))
+        return fail(GNNGLS_ERR_ARG, "insertion: mode GNNGLS_INSERT_GIVEN_ORDER needs order and status");
+    if (n > GNNGLS_INSERTION_MAX_N)
+        return fail(GNNGLS_ERR_UNSUPPORTED, "insertion: n=%d exceeds the largest supported instance (n <= %d: the tour state of an instance lives in LDS)",
+                    n, GNNGLS_INSERTION_MAX_N);
+    ProfScope ps(GNNGLS_PROF_INSERTION, (hipStream_t)stream);
+    hipError_t e = gnngls::launch_insertion(W, B, n, depot, mode, order, tour_out, status, (hipStream_t)stream);
+    return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "insertion");
+}
+
+int gnngls_cheapest_insertion(const int32_t *sub_tour, int len, const int32_t *node, const double *W, int B, int n,
+                              int32_t *tour_out, double *cost_out, void *stream) {
+    if (B == 0) return GNNGLS_OK;
+    if (!sub_tour || !node || !W || !tour_out || !cost_out) return fail(GNNGLS_ERR_ARG, "cheapest_insertion: NULL pointer");
+    if (B < 0) return fail(GNNGLS_ERR_ARG, "cheapest_insertion: B=%d must be >= 0", B);
+    if (n < 1) return fail(GNNGLS_ERR_ARG, "cheapest_insertion: n=%d must be >= 1", n);
+    if (len < 2 || len > n) return fail(GNNGLS_ERR_ARG, "cheapest_insertion: len=%d out of range (2..n=%d)", len, n);
+    if (n > GNNGLS_INSERTION_MAX_N)
+        return fail(GNNGLS_ERR_UNSUPPORTED, "cheapest_insertion: n=%d exceeds the largest supported instance (n <= %d)", n,
+                    GNNGLS_INSERTION_MAX_N);
+    ProfScope ps(GNNGLS_PROF_INSERTION, (hipStream_t)stream);
+    hipError_t e = gnngls::launch_cheapest_insertion(sub_tour, len, node, W, B, n, tour_out, cost_out, (hipStream_t)stream);
+    return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "cheapest_insertion");
 }
 
 int gnngls_gls_run(const double *D, const double *guides, int n_guides, int B, int n,

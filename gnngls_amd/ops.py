@@ -89,6 +89,73 @@ def nearest_neighbor(W, depot=0):
     return out
 
 
+INSERT_MODES = {"nearest": 0, "farthest": 1, "random": 2}    # GNNGLS_INSERT_* (mode 'random' = GNNGLS_INSERT_GIVEN_ORDER)
+INSERTION_MAX_N = 2048                                        # GNNGLS_INSERTION_MAX_N
+STATUS_BAD_ORDER = 5
+
+
+def random_order(n, depot=0):
+    """The node order of insertion(G, depot, mode='random') (reference algorithms.py:85-91,105): np.random.choice on the
+    shrinking list of outside nodes.  The draws do not depend on the tour, so they are made here with the very same calls:
+    the same nodes, and NumPy's global stream is left where the reference leaves it."""
+    import numpy as np
+    nodes = list(range(n))
+    nodes.remove(depot)
+    order = []
+    while len(nodes) > 0:
+        next_node = np.random.choice(nodes)
+        nodes.remove(next_node)
+        order.append(int(next_node))
+    return order
+
+
+def insertion(W, depot=0, mode="farthest", order=None):
+    """W [B,n,n] fp64 -> tours [B,n+1] int32 (reference algorithms.py:82-108), one launch for the whole batch.
+    mode 'nearest' / 'farthest': algorithms.py:93-103.  mode 'random': `order` [B,n-1] int32 gives every instance's node
+    order; None draws it per instance with random_order (the reference's np.random.choice calls, in batch order).
+    A row of `order` that is not a permutation of the non-depot nodes raises."""
+    assert mode in INSERT_MODES, f"Unknown mode: {mode}"
+    B, n, n2 = W.shape
+    assert n == n2 and W.dtype == torch.float64
+    out = torch.empty((B, n + 1), dtype=torch.int32, device=W.device)
+    status = None
+    if mode == "random":
+        if order is None:
+            order = torch.tensor([random_order(n, int(depot)) for _ in range(B)], dtype=torch.int32).reshape(B, n - 1)
+        order = order.to(device=W.device, dtype=torch.int32).contiguous()
+        assert order.shape == (B, n - 1), f"order shape {tuple(order.shape)} is not [{B},{n - 1}]"
+        status = torch.zeros((B,), dtype=torch.int32, device=W.device)
+    else:
+        assert order is None, "order is only read in mode 'random'"
+    L = _lib.load()
+    _lib.check(L.gnngls_insertion(_lib.ptr(W), B, n, int(depot), INSERT_MODES[mode], _lib.ptr(order) if n > 1 else None,
+                                  _lib.ptr(out), _lib.ptr(status), _lib.current_stream()), "insertion")
+    if status is not None:
+        bad = status.nonzero().flatten().tolist()
+        if bad:
+            raise ValueError(f"insertion: order rows {bad[:8]} are not permutations of the non-depot nodes "
+                             f"(status {STATUS_BAD_ORDER})")
+    return out
+
+
+def cheapest_insertion(sub_tour, node, W):
+    """sub_tour [B,len] int32, node [B] int32, W [B,n,n] fp64 -> (tours [B,len+1] int32, cost [B] fp64): the first position whose
+    candidate tour has the strictly smallest tour_cost (reference algorithms.py:67-79), and that cost."""
+    B, n, n2 = W.shape
+    assert n == n2 and W.dtype == torch.float64
+    assert sub_tour.dtype == torch.int32 and sub_tour.dim() == 2 and sub_tour.shape[0] == B
+    assert node.dtype == torch.int32 and node.shape == (B,)
+    ln = sub_tour.shape[1]
+    out = torch.empty((B, ln + 1), dtype=torch.int32, device=W.device)
+    cost = torch.zeros((B,), dtype=torch.float64, device=W.device)
+    L = _lib.load()
+    _lib.check(L.gnngls_cheapest_insertion(_lib.ptr(sub_tour), ln, _lib.ptr(node), _lib.ptr(W), B, n, _lib.ptr(out), _lib.ptr(cost),
+                                           _lib.current_stream()), "cheapest_insertion")
+    if bool(torch.isnan(cost).any()):
+        raise ValueError("cheapest_insertion: a sub-tour or node index is out of 0..n-1 (or a weight is NaN)")
+    return out, cost
+
+
 @dataclass
 class GlsResult:
     best_tour: torch.Tensor      # [B,n+1] int32

@@ -2,7 +2,8 @@
 for B independent instances at once, entirely on the GPU.
 
     features (datasets.py:73-95) -> model forward (test.py:76-77) -> inverse scaler + clamp
-    (test.py:79-83) -> nearest_neighbor on the guide (test.py:85) -> tour_cost (test.py:90)
+    (test.py:79-83) -> start tour on the guide: nearest_neighbor (test.py:85) or an insertion constructor
+    (algorithms.py:82-108) -> tour_cost (test.py:90)
     -> guided_local_search with the remaining budget (test.py:91-95)
 
 The 10 s budget of the reference starts before the forward pass (test.py:64), so the search gets
@@ -69,6 +70,10 @@ class SolveResult:
     launch_time: torch.Tensor = None   # [B] fp64 host time.time() just before its search kernel was launched
 
 
+# start tours of solve_batch -> mode of ops.insertion (None: ops.nearest_neighbor)
+INIT_TOURS = {"nearest_neighbor": None, "nearest_insertion": "nearest", "farthest_insertion": "farthest"}
+
+
 def predict_regret(model, D, scalers, features=None):
     """-> 'regret_pred' guide matrices [B,n,n] fp64 (test.py:72-83).
     features: None = the reference's default feature set, the scaled edge weight (datasets.py:14-20 set_features), packed
@@ -87,7 +92,8 @@ def predict_regret(model, D, scalers, features=None):
 
 def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit=10.0, perturbation_moves=20,
                 first_improvement=False, max_outer_iters=-1, trace_cap=0, want_trace_time=False, chunk=None,
-                keep_regret=False, budget="per_instance", imp_cap=0, features=None, count_executed=False):
+                keep_regret=False, budget="per_instance", imp_cap=0, features=None, count_executed=False,
+                init="nearest_neighbor", init_weight="auto"):
     """D [B,n,n] fp64 CUDA tensor (symmetric).  Returns SolveResult with per-instance tensors.
 
     budget="per_instance" (default, the reference's meaning of --time_limit, test.py:64,92): every instance is searched
@@ -95,7 +101,16 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
     budget="per_batch": the whole batch finishes within `time_limit`; the rounds share it equally (each instance is
     searched for time_limit / rounds) -- the throughput end of the same trade, with the gap there to judge it.
     features: see predict_regret (None = scaled edge weights packed on the device).
-    count_executed: also return the delta evaluations the search kernel actually executed (bench.py's roofline)."""
+    count_executed: also return the delta evaluations the search kernel actually executed (bench.py's roofline).
+    init: the start tour -- "nearest_neighbor" (test.py:85), "nearest_insertion" or "farthest_insertion" (the reference's
+    insertion(G, depot, mode), algorithms.py:82-108), from depot 0.
+    init_weight: the matrix the start tour is built on.  "auto" keeps the reference's rule (test.py:70-88: 'regret_pred'
+    whenever that guide is used at all, else 'weight'); "weight" builds it on the distances even when the model guides the search."""
+    if init not in INIT_TOURS:
+        raise ValueError(f"unknown start tour {init!r} (one of {', '.join(INIT_TOURS)})")
+    if init_weight not in ("auto", "weight"):
+        raise ValueError(f"unknown init_weight {init_weight!r} ('auto' or 'weight')")
+    insert_mode = INIT_TOURS[init]
     if budget not in ("per_instance", "per_batch"):
         raise ValueError(f"unknown budget policy {budget!r}")
     assert D.is_cuda and D.dtype == torch.float64
@@ -134,7 +149,9 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
         t1 = time.time()
         # test.py:70-88: the start tour is greedy on 'regret_pred' whenever that guide is used AT ALL (not only when it
         # comes first), otherwise on 'weight'
-        init = ops.nearest_neighbor(R if need_model else Dc)
+        Wi = R if (need_model and init_weight == "auto") else Dc
+        # the defaults give nearest_neighbor(R if need_model else Dc): the call this function always made
+        init = ops.nearest_neighbor(Wi) if insert_mode is None else ops.insertion(Wi, 0, insert_mode)
         init_cost = ops.tour_cost(init, Dc)                                # test.py:90
         gt = torch.stack([R if g == "regret_pred" else Dc for g in guides]).contiguous()
         torch.cuda.synchronize()

@@ -1,6 +1,6 @@
 """PyTorch-ROCm custom operators of the hot path: `torch.ops.gnngls.*` (north_star).
 
-Five operators are registered with `torch.library` over the C ABI of libgnngls_hip.so (include/gnngls_hip.h).  Each has
+Seven operators are registered with `torch.library` over the C ABI of libgnngls_hip.so (include/gnngls_hip.h).  Each has
 exactly ONE implementation, for the CUDA dispatch key (= HIP on ROCm): there is no CPU kernel behind any of them, so
 calling one with CPU tensors fails in the dispatcher ("no CPU fallback" is structural, not a runtime check).  Shape
 functions (fake/meta kernels) are registered so the ops can be traced and used under FakeTensorMode.  All ops enqueue on
@@ -15,6 +15,9 @@ the current HIP stream, take caller-owned contiguous tensors and retain nothing.
     gls_run(D, guides[G,B,n,n] f64, init_tour, init_cost, perturbation_moves, max_outer_iters, time_limit_s,
             first_improvement, trace_capacity) -> (best_tour, best_cost, outer_iters[B] i64, trace_cost[B,T] f64,
             trace_len[B] i32)                                                      algorithms.py:135-195
+    insertion(W[B,n,n] f64, depot, mode, order[B,n-1] i32 or None) -> tour[B,n+1] i32          algorithms.py:82-108
+        mode in {'nearest', 'farthest', 'random'}; 'random' takes the node order (None: drawn with np.random.choice)
+    cheapest_insertion(sub_tour[B,len] i32, node[B] i32, W) -> (tour[B,len+1] i32, cost[B] f64)   algorithms.py:67-79
 """
 import ctypes
 
@@ -30,6 +33,8 @@ _LIB.define("local_search(Tensor tour, Tensor cost, Tensor D, bool first_improve
 _LIB.define("gls_run(Tensor D, Tensor guides, Tensor init_tour, Tensor init_cost, int perturbation_moves, "
             "int max_outer_iters, float time_limit_s, bool first_improvement, int trace_capacity) "
             "-> (Tensor, Tensor, Tensor, Tensor, Tensor)")
+_LIB.define("insertion(Tensor W, int depot, str mode, Tensor? order) -> Tensor")
+_LIB.define("cheapest_insertion(Tensor sub_tour, Tensor node, Tensor W) -> (Tensor, Tensor)")
 
 _workspaces = {}      # device index -> uint8 scratch tensor for the forward (grown on demand, reused across calls)
 
@@ -87,6 +92,8 @@ _LIB.impl("two_opt_delta_all", ops.two_opt_delta_all, "CUDA")
 _LIB.impl("relocate_delta_all", ops.relocate_delta_all, "CUDA")
 _LIB.impl("local_search", _local_search, "CUDA")
 _LIB.impl("gls_run", _gls_run, "CUDA")
+_LIB.impl("insertion", ops.insertion, "CUDA")
+_LIB.impl("cheapest_insertion", ops.cheapest_insertion, "CUDA")
 
 
 # ---- shape functions (fake tensors / tracing); no arithmetic -------------------------------------------------------
@@ -116,3 +123,13 @@ def _(D, guides, init_tour, init_cost, perturbation_moves, max_outer_iters, time
     B = D.shape[0]
     return (torch.empty_like(init_tour), torch.empty_like(init_cost), D.new_empty((B,), dtype=torch.int64),
             D.new_empty((B, trace_capacity), dtype=torch.float64), D.new_empty((B,), dtype=torch.int32))
+
+
+@torch.library.register_fake("gnngls::insertion")
+def _(W, depot, mode, order):
+    return W.new_empty((W.shape[0], W.shape[1] + 1), dtype=torch.int32)
+
+
+@torch.library.register_fake("gnngls::cheapest_insertion")
+def _(sub_tour, node, W):
+    return sub_tour.new_empty((sub_tour.shape[0], sub_tour.shape[1] + 1)), W.new_empty((W.shape[0],), dtype=torch.float64)

@@ -46,6 +46,8 @@ extern "C" {
                                          and the search would differ; rerun the instance with penalty_bits = -1 */
 #define GNNGLS_STATUS_EDGE_LOST 4     /* gnngls_regret_labels: a fixed-edge search returned a tour without its edge (never expected:
                                          see there); that edge keeps its earlier label */
+#define GNNGLS_STATUS_BAD_ORDER 5     /* gnngls_insertion, GNNGLS_INSERT_GIVEN_ORDER: the instance's row of `order` is not a
+                                         permutation of the non-depot nodes; its tour row was left untouched */
 
 int gnngls_abi_version(void);
 const char *gnngls_last_error(void);
@@ -101,6 +103,41 @@ int gnngls_tour_cost(const int32_t *tour, const double *D, int B, int n, double 
 
 /* ---- nearest_neighbor (algorithms.py:9-18) on a dense weight matrix W[B,n,n]; ties -> lowest id */
 int gnngls_nearest_neighbor(const double *W, int B, int n, int depot, int32_t *tour_out, void *stream);
+
+/* ---- insertion (algorithms.py:82-108): the closed tour grows from [depot, depot] by one node per step ---------------------
+ * mode GNNGLS_INSERT_NEAREST / _FARTHEST: the next node is the outside node j of the pair (tour member i, j) with the smallest /
+ *      largest W[i,j] (algorithms.py:93-103: `for i in tour: for j in nodes` with a strict compare, so ties go to the smallest
+ *      tour position of i, then to the smallest j);
+ * mode GNNGLS_INSERT_GIVEN_ORDER: the next node is order[b][step] -- mode 'random' of the reference (algorithms.py:90-91),
+ *      whose np.random.choice draws do not depend on the tour; the caller makes them on the host (gnngls_amd.ops.random_order).
+ * Each node goes where cheapest_insertion (below) puts it.
+ *   W         [B,n,n] fp64, finite; the reference reads an undirected graph, so only symmetric matrices are pinned to it: the
+ *             kernel reads W[t[p], t[p+1]] in tour direction and W[i,j] with i the tour member.  With NaN weights the tours
+ *             are unspecified (every index stays in range).
+ *   order     [B,n-1] int32 and status [B]: required for GNNGLS_INSERT_GIVEN_ORDER only (status, when given, is written 0 in the
+ *             other modes).  The kernel checks every row of `order` to be a permutation of the non-depot nodes BEFORE it uses an
+ *             entry as an index: a bad row gets status GNNGLS_STATUS_BAD_ORDER, its row of tour_out is left untouched and
+ *             nothing is read or written out of range.
+ *   tour_out  [B,n+1]; n = 1 gives [d, d], n = 2 gives [d, x, d].
+ * 1 <= n <= GNNGLS_INSERTION_MAX_N (one workgroup per instance, 48 B of LDS per node); a larger n returns
+ * GNNGLS_ERR_UNSUPPORTED.  Bad arguments are rejected on the host before any device work; B == 0 returns GNNGLS_OK. */
+#define GNNGLS_INSERT_NEAREST 0
+#define GNNGLS_INSERT_FARTHEST 1
+#define GNNGLS_INSERT_GIVEN_ORDER 2
+#define GNNGLS_INSERTION_MAX_N 2048
+int gnngls_insertion(const double *W, int B, int n, int depot, int mode, const int32_t *order, int32_t *tour_out,
+                     int32_t *status, void *stream);
+
+/* ---- cheapest_insertion (algorithms.py:67-79): one step on a caller's sub-tour ------------------------------------------------
+ * For every position j = 1 .. len-1 the candidate is sub_tour with `node` inserted at j; its cost is tour_cost
+ * (gnngls/__init__.py:17-21): the left-to-right fp64 sum of ALL its edge weights, not a difference against the old tour.  The
+ * first j whose cost is strictly smallest wins (algorithms.py:76).
+ *   sub_tour  [B,len] int32 (any node list, usually closed: [d, ..., d]), 2 <= len <= n (the reference returns None for
+ *             len < 2: gnngls_amd.algorithms does that on the host); node [B]; W [B,n,n] as above, 1 <= n <= GNNGLS_INSERTION_MAX_N
+ *   tour_out  [B,len+1], cost_out [B] the winning candidate's tour_cost.  An instance with an index out of 0..n-1 in its
+ *             sub-tour or node gets cost NaN and its tour row untouched; nothing is read out of range. */
+int gnngls_cheapest_insertion(const int32_t *sub_tour, int len, const int32_t *node, const double *W, int B, int n,
+                              int32_t *tour_out, double *cost_out, void *stream);
 
 /* ---- K3: guided_local_search (algorithms.py:135-195), local_search (algorithms.py:111-132) -----
  * One persistent workgroup per instance.
@@ -329,7 +366,7 @@ enum {
     GNNGLS_PROF_GEMM_FFN1, GNNGLS_PROF_GEMM_FFN2, GNNGLS_PROF_DECISION, GNNGLS_PROF_UNPACK,
     GNNGLS_PROF_NEAREST_NEIGHBOR, GNNGLS_PROF_TOUR_COST, GNNGLS_PROF_GLS, GNNGLS_PROF_FFN_FUSED,
     GNNGLS_PROF_TRAIN_COLSUM, GNNGLS_PROF_TRAIN_ELEMENTWISE, GNNGLS_PROF_TRAIN_GEMM_BWD, GNNGLS_PROF_TRAIN_GEMM_TN,
-    GNNGLS_PROF_TRAIN_GAT_BWD, GNNGLS_PROF_KINDS
+    GNNGLS_PROF_TRAIN_GAT_BWD, GNNGLS_PROF_INSERTION /* gnngls_insertion and gnngls_cheapest_insertion */, GNNGLS_PROF_KINDS
 };
 int gnngls_profile_enable(int on);
 int gnngls_profile_collect(double *ms_by_kind, int64_t *launches_by_kind);

@@ -5,7 +5,8 @@
 [--use_gpu]`, per-instance semantics unchanged (the budget starts before the forward pass, nearest-neighbour start
 on 'regret_pred' whenever that guide is used and on 'weight' otherwise (test.py:70-88), guided_local_search, gap vs the
 optimum stored in the instances) and the same DataFrame pickle (columns instance, time, opt_cost, cost, best_cost, gap,
-dt) in `run_dir/<timestamp>_<uuid>.pkl`.
+dt) in `run_dir/<timestamp>_<uuid>.pkl`.  `--init_tour nearest_insertion|farthest_insertion` starts from the reference's insertion
+constructors (algorithms.py:82-108) instead, `--init_weight weight` builds the start on the distances whatever the guide.
 
 Search progress (test.py:97-117).  The reference appends one row per accepted move; a 10 s TSP100 search on the GPU
 accepts ~2e6 moves per instance, i.e. ~20 GB of rows for a 1024-instance batch.  The default record here is therefore
@@ -61,6 +62,12 @@ def parse_args():
                              'instead of giving every instance the full budget')
     parser.add_argument('--full_trace', type=int, default=0, metavar='CAP',
                         help='also record the first CAP accepted moves of every instance (the reference records all)')
+    parser.add_argument('--init_tour', type=str, default='nearest_neighbor', choices=list(pipeline.INIT_TOURS),
+                        help='start tour: the reference\'s nearest_neighbor (test.py:85) or one of its insertion '
+                             'constructors (algorithms.py:82-108)')
+    parser.add_argument('--init_weight', type=str, default='auto', choices=['auto', 'weight'],
+                        help="matrix the start tour is built on: auto = regret_pred whenever that guide is used, else weight "
+                             "(test.py:70-88); weight = always the distances")
     return parser.parse_args()
 
 
@@ -126,7 +133,8 @@ def solve_block(names, test_set, model, scalers, args, chunk, budget='per_instan
     res = pipeline.solve_batch(D, model, scalers, guides=args.guides, time_limit=args.time_limit,
                                perturbation_moves=args.perturbation_moves, trace_cap=args.full_trace,
                                want_trace_time=args.full_trace > 0, chunk=chunk, budget=budget, imp_cap=IMP_CAP,
-                               features=features)
+                               features=features, init=getattr(args, 'init_tour', 'nearest_neighbor'),
+                               init_weight=getattr(args, 'init_weight', 'auto'))
     res.imp_cost, res.imp_time, res.imp_len = res.imp_cost.cpu(), res.imp_time.cpu(), res.imp_len.cpu()
     res.moves = res.moves.cpu()
     if args.full_trace > 0:
