@@ -30,6 +30,8 @@ SIGNATURES = {
     "gnngls_nearest_neighbor": [_vp, _int, _int, _int, _vp, _vp],
     "gnngls_insertion": [_vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp],
     "gnngls_cheapest_insertion": [_vp, _int, _vp, _vp, _int, _int, _vp, _vp, _vp],
+    "gnngls_one_tree_bound": [_vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gnngls_one_tree_bound_describe": [_int, _vp, _vp, _vp],
     "gnngls_gls_run": [_vp, _vp, _int, _int, _int, _vp, _vp, _int, _int, _int, _i64, _f64, _f64,
                        _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp],
     "gnngls_model_packed_floats": [_int, _int],
@@ -68,6 +70,8 @@ SIGNATURES = {
 PROF_KINDS = ["pack_features", "embed", "gemm_fc", "gat_rows", "gat_rows_rank1", "gemm_ffn1(unused)", "gemm_ffn2(unused)",
               "decision", "unpack_regret", "nearest_neighbor", "tour_cost", "gls", "ffn_fused",
               "train_colsum", "train_elementwise", "train_gemm_bwd", "train_gemm_tn", "train_gat_bwd", "insertion"]
+# kinds of entries added after the constructors (GNNGLS_PROF_* in the header's order, behind PROF_KINDS: no index moved)
+PROF_KINDS_BOUNDS = ["one_tree_bound"]
 
 
 def profile_enable(on=True):
@@ -76,12 +80,13 @@ def profile_enable(on=True):
 
 def profile_collect():
     """-> {kind: (milliseconds, launches)} since profile_enable(True)."""
-    n = len(PROF_KINDS)
+    kinds = PROF_KINDS + (PROF_KINDS_BOUNDS if hasattr(load(), "gnngls_one_tree_bound") else [])
+    n = len(kinds)
     ms = (ctypes.c_double * n)()
     cnt = (ctypes.c_int64 * n)()
     check(load().gnngls_profile_collect(ctypes.cast(ms, ctypes.c_void_p), ctypes.cast(cnt, ctypes.c_void_p)),
           "profile_collect")
-    return {k: (ms[i], cnt[i]) for i, k in enumerate(PROF_KINDS)}
+    return {k: (ms[i], cnt[i]) for i, k in enumerate(kinds)}
 _RESTYPES = {"gnngls_last_error": ctypes.c_char_p, "gnngls_model_packed_floats": ctypes.c_int64,
              "gnngls_regret_forward_workspace_bytes": ctypes.c_int64,
              "gnngls_regret_prepared_bytes": ctypes.c_int64,
@@ -96,6 +101,8 @@ _HEADS = ("gnngls_model_heads_supported", "gnngls_regret_forward_workspace_bytes
           "gnngls_regret_train_forward_heads", "gnngls_regret_train_backward_heads")
 # the insertion tour constructors (an older build named by GNNGLS_HIP_SO lacks them; ops.insertion then raises)
 _CONSTRUCTORS = ("gnngls_insertion", "gnngls_cheapest_insertion")
+# the Held-Karp 1-tree bound (an older build named by GNNGLS_HIP_SO lacks it; ops.one_tree_bound then raises)
+_BOUNDS = ("gnngls_one_tree_bound", "gnngls_one_tree_bound_describe")
 _lib = None
 
 
@@ -118,7 +125,7 @@ def load():
         import torch  # noqa: F401
         L = ctypes.CDLL(SO)
         for name, argtypes in SIGNATURES.items():
-            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
+            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS or name in _BOUNDS) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
                 continue              # an older build of the library named by GNNGLS_HIP_SO (same-box A/B of kernel variants)
             f = getattr(L, name)      # AttributeError if the symbol is missing
             f.argtypes = argtypes

@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 SO = os.path.join(HERE, "libgnngls_hip.so")
 SOURCES = ["gls_kernels.hip", "model_kernels.hip", "train_kernels.hip", "heads_kernels.hip", "labels_kernels.hip", "constructors_kernels.hip",
-           "capi.hip"]
+           "bounds_kernels.hip", "capi.hip"]
 # -ffp-contract=off: the guided matrix D + k*P (gnngls/algorithms.py:164) rounds twice and np.isclose
 # (operators.py:42) is evaluated literally; a fused multiply-add would change move selection.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result"]
@@ -29,8 +29,9 @@ HEADERS = {
     "heads_kernels.hip": ["heads_kernels.h"],
     "labels_kernels.hip": ["labels_kernels.h", "gls_kernels.h"],
     "constructors_kernels.hip": ["constructors_kernels.h", "gls_common.h"],
+    "bounds_kernels.hip": ["bounds_kernels.h", "gls_common.h"],
     "capi.hip": ["gls_kernels.h", "model_kernels.h", "train_kernels.h", "heads_kernels.h", "labels_kernels.h", "constructors_kernels.h",
-                 os.path.join("..", "..", "include", "gnngls_hip.h")],
+                 "bounds_kernels.h", os.path.join("..", "..", "include", "gnngls_hip.h")],
 }
 
 

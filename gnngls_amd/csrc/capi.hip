@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/gnngls_hip.h"
+#include "bounds_kernels.h"
 #include "constructors_kernels.h"
 #include "gls_kernels.h"
 #include "heads_kernels.h"
@@ -321,6 +322,36 @@ int gnngls_cheapest_insertion(const int32_t *sub_tour, int len, const int32_t *n
     ProfScope ps(GNNGLS_PROF_INSERTION, (hipStream_t)stream);
     hipError_t e = gnngls::launch_cheapest_insertion(sub_tour, len, node, W, B, n, tour_out, cost_out, (hipStream_t)stream);
     return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "cheapest_insertion");
+}
+
+static_assert(GNNGLS_ONE_TREE_MAX_N == gnngls::kOneTreeMaxN, "include/gnngls_hip.h and bounds_kernels.h disagree");
+static_assert(GNNGLS_BOUND_EXIT_ITERS == gnngls::BOUND_EXIT_ITERS && GNNGLS_BOUND_EXIT_STEP == gnngls::BOUND_EXIT_STEP &&
+              GNNGLS_BOUND_EXIT_TOUR == gnngls::BOUND_EXIT_TOUR && GNNGLS_STATUS_ASYMMETRIC == GNNGLS_STATUS_ASYMMETRIC_DEV,
+              "include/gnngls_hip.h and bounds_kernels.h disagree");
+
+int gnngls_one_tree_bound(const double *D, const double *ub, int B, int n, int max_iters, double *bound, double *pi, int32_t *iters,
+                          int32_t *exit_kind, int32_t *status, void *stream) {
+    if (B < 0) return fail(GNNGLS_ERR_ARG, "one_tree_bound: B=%d must be >= 0", B);
+    if (n < 3) return fail(GNNGLS_ERR_ARG, "one_tree_bound: n=%d must be >= 3", n);
+    if (n > GNNGLS_ONE_TREE_MAX_N)
+        return fail(GNNGLS_ERR_UNSUPPORTED, "one_tree_bound: n=%d exceeds the largest supported instance (n <= %d: the ascent state of an "
+                    "instance lives in the registers of one workgroup)", n, GNNGLS_ONE_TREE_MAX_N);
+    if (max_iters < 0) return fail(GNNGLS_ERR_ARG, "one_tree_bound: max_iters=%d must be >= 0", max_iters);
+    if (B == 0) return GNNGLS_OK;
+    if (!D || !ub || !bound || !iters || !exit_kind || !status)
+        return fail(GNNGLS_ERR_ARG, "one_tree_bound: NULL pointer (D, ub, bound, iters, exit_kind, status)");
+    ProfScope ps(GNNGLS_PROF_ONE_TREE_BOUND, (hipStream_t)stream);
+    hipError_t e = gnngls::launch_one_tree_bound(D, ub, B, n, max_iters, bound, pi, iters, exit_kind, status, (hipStream_t)stream);
+    return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "one_tree_bound");
+}
+
+int gnngls_one_tree_bound_describe(int n, int *threads, int *lds_bytes, int *nodes_per_lane) {
+    if (n < 3 || n > GNNGLS_ONE_TREE_MAX_N) return fail(GNNGLS_ERR_ARG, "one_tree_bound_describe: n=%d out of range (3..%d)", n, GNNGLS_ONE_TREE_MAX_N);
+    const int t = gnngls::one_tree_threads(n);
+    if (threads) *threads = t;
+    if (lds_bytes) *lds_bytes = gnngls::one_tree_lds_bytes(n);
+    if (nodes_per_lane) *nodes_per_lane = t > 64 ? 4 : (n + 63) / 64;
+    return GNNGLS_OK;
 }
 
 int gnngls_gls_run(const double *D, const double *guides, int n_guides, int B, int n,

@@ -182,6 +182,55 @@ class GlsResult:
 STATUS_OK, STATUS_WATCHDOG, STATUS_PENALTY_OVERFLOW, STATUS_ASYMMETRIC = 0, 1, 2, 3
 
 
+ONE_TREE_MAX_N = 1024                                         # GNNGLS_ONE_TREE_MAX_N
+BOUND_EXIT_ITERS, BOUND_EXIT_STEP, BOUND_EXIT_TOUR = 0, 1, 2  # GNNGLS_BOUND_EXIT_*
+
+
+@dataclass
+class OneTreeResult:
+    bound: torch.Tensor          # [B] fp64: max_k w(pi_k) <= the optimal tour length
+    pi: torch.Tensor             # [B,n] fp64 potentials that attain it, or None
+    iters: torch.Tensor          # [B] int32 1-trees built
+    exit_kind: torch.Tensor      # [B] int32 BOUND_EXIT_* (TOUR: the bound is the optimum)
+    status: torch.Tensor         # [B] int32
+
+
+def one_tree_bound(D, ub, max_iters=2000, want_pi=True):
+    """Held-Karp 1-tree lower bounds of the optimal tour lengths of a batch, one launch (oracle/one_tree.c bit for bit; stands in
+    for Concorde's optimum in the reference's gap, scripts/test.py:62,104).  D [B,n,n] fp64 bitwise symmetric, ub [B] fp64 the
+    length of any tour per instance (steers the step size only).  A matrix that is not symmetric raises."""
+    B, n, n2 = D.shape
+    assert n == n2 and D.dtype == torch.float64
+    assert ub.dtype == torch.float64 and ub.shape == (B,), f"ub shape {tuple(ub.shape)} is not [{B}]"
+    dev = D.device
+    bound = torch.empty((B,), dtype=torch.float64, device=dev)
+    pi = torch.zeros((B, n), dtype=torch.float64, device=dev) if want_pi else None
+    iters = torch.zeros((B,), dtype=torch.int32, device=dev)
+    exit_kind = torch.zeros((B,), dtype=torch.int32, device=dev)
+    status = torch.zeros((B,), dtype=torch.int32, device=dev)
+    L = _lib.load()
+    if not hasattr(L, "gnngls_one_tree_bound"):
+        raise _lib.GnnglsHipError("this build of libgnngls_hip.so has no gnngls_one_tree_bound")
+    _lib.check(L.gnngls_one_tree_bound(_lib.ptr(D.contiguous()), _lib.ptr(ub.contiguous()), B, n, int(max_iters), _lib.ptr(bound),
+                                       _lib.ptr(pi), _lib.ptr(iters), _lib.ptr(exit_kind), _lib.ptr(status), _lib.current_stream()),
+               "one_tree_bound")
+    bad = (status == STATUS_ASYMMETRIC).nonzero().flatten().tolist()
+    if bad:
+        raise ValueError(f"one_tree_bound: the matrices of instances {bad[:8]} are not bitwise symmetric (status {STATUS_ASYMMETRIC}): "
+                         "the 1-tree bound is a bound for symmetric costs only")
+    return OneTreeResult(bound, pi, iters, exit_kind, status)
+
+
+def one_tree_describe(n):
+    """-> dict(threads, lds_bytes, nodes_per_lane, form) of the launch one_tree_bound makes for n nodes (host-side query)."""
+    vals = [ctypes.c_int(0) for _ in range(3)]
+    _lib.check(_lib.load().gnngls_one_tree_bound_describe(int(n), *[ctypes.cast(ctypes.byref(v), ctypes.c_void_p) for v in vals]),
+               "one_tree_bound_describe")
+    t, lds, slots = (v.value for v in vals)
+    return {"threads": t, "lds_bytes": lds, "nodes_per_lane": slots,
+            "form": f"{t // 64} wavefront(s) per instance, {slots} node(s) per lane in registers, matrix rows from global memory"}
+
+
 def gls_run(D, guides, init_tour, init_cost, perturbation_moves=30, first_improvement=False,
             max_outer_iters=-1, time_limit_s=0.0, watchdog_s=None, trace_cap=0, want_trace_time=False,
             want_penalty=False, penalty_bits=0, retry_overflow=True, imp_cap=0, retry_asymmetric=True):

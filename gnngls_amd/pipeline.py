@@ -68,6 +68,10 @@ class SolveResult:
     evals_executed: torch.Tensor = None   # [B] int64, only with count_executed (measurement hook, ops.executed_evals)
     start_time: torch.Tensor = None    # [B] fp64 host time.time() at which the instance's budget started (test.py:64)
     launch_time: torch.Tensor = None   # [B] fp64 host time.time() just before its search kernel was launched
+    # only with lower_bound=True: the Held-Karp 1-tree bound of every instance (ops.one_tree_bound with ub = best_cost), a
+    # certified lower_bound <= optimum <= best_cost, and how its ascent ended (ops.BOUND_EXIT_*; TOUR: the bound is the optimum)
+    lower_bound: torch.Tensor = None   # [B] fp64
+    bound_exit: torch.Tensor = None    # [B] int32
 
 
 # start tours of solve_batch -> mode of ops.insertion (None: ops.nearest_neighbor)
@@ -93,7 +97,7 @@ def predict_regret(model, D, scalers, features=None):
 def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit=10.0, perturbation_moves=20,
                 first_improvement=False, max_outer_iters=-1, trace_cap=0, want_trace_time=False, chunk=None,
                 keep_regret=False, budget="per_instance", imp_cap=0, features=None, count_executed=False,
-                init="nearest_neighbor", init_weight="auto"):
+                init="nearest_neighbor", init_weight="auto", lower_bound=False, bound_iters=2000):
     """D [B,n,n] fp64 CUDA tensor (symmetric).  Returns SolveResult with per-instance tensors.
 
     budget="per_instance" (default, the reference's meaning of --time_limit, test.py:64,92): every instance is searched
@@ -105,7 +109,9 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
     init: the start tour -- "nearest_neighbor" (test.py:85), "nearest_insertion" or "farthest_insertion" (the reference's
     insertion(G, depot, mode), algorithms.py:82-108), from depot 0.
     init_weight: the matrix the start tour is built on.  "auto" keeps the reference's rule (test.py:70-88: 'regret_pred'
-    whenever that guide is used at all, else 'weight'); "weight" builds it on the distances even when the model guides the search."""
+    whenever that guide is used at all, else 'weight'); "weight" builds it on the distances even when the model guides the search.
+    lower_bound: after a chunk's search has ended (outside its budget) also compute the Held-Karp 1-tree bound of its instances
+    with at most `bound_iters` 1-trees and ub = best_cost -> SolveResult.lower_bound, .bound_exit and timing["bound_s"]."""
     if init not in INIT_TOURS:
         raise ValueError(f"unknown start tour {init!r} (one of {', '.join(INIT_TOURS)})")
     if init_weight not in ("auto", "weight"):
@@ -128,7 +134,8 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
         return SolveResult(best_tour=torch.zeros((0, n + 1), dtype=torch.int32, device=D.device), best_cost=e64,
                            init_cost=e64, outer_iters=ei64, evals=ei64, moves=ei32, status=ei32,
                            timing={"forward_s": 0.0, "init_s": 0.0, "search_s": 0.0, "chunks": 0},
-                           start_time=e64.cpu(), launch_time=e64.cpu())
+                           start_time=e64.cpu(), launch_time=e64.cpu(), lower_bound=e64 if lower_bound else None,
+                           bound_exit=ei32 if lower_bound else None)
     cap = ops.gls_resident_capacity(n)
     if chunk is None:
         chunk = cap if cap > 0 else 64
@@ -178,9 +185,14 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
         timing["init_s"] += t2 - t1
         timing["search_s"] += t3 - t2
         timing["chunks"] += 1
+        lb = None
+        if lower_bound:
+            lb = ops.one_tree_bound(Dc, r.best_cost, max_iters=bound_iters, want_pi=False)
+            torch.cuda.synchronize()
+            timing["bound_s"] = timing.get("bound_s", 0.0) + (time.time() - t3)
         outs.append((r, init_cost, R if keep_regret else None,
                      torch.full((Dc.shape[0],), t0, dtype=torch.float64), torch.full((Dc.shape[0],), t2, dtype=torch.float64),
-                     executed))
+                     executed, lb))
     cat = lambda xs: torch.cat(xs) if len(xs) > 1 else xs[0]  # noqa: E731
     return SolveResult(
         best_tour=cat([o[0].best_tour for o in outs]), best_cost=cat([o[0].best_cost for o in outs]),
@@ -195,7 +207,9 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
         imp_iter=cat([o[0].imp_iter for o in outs]) if imp_cap > 0 else None,
         imp_len=cat([o[0].imp_len for o in outs]) if imp_cap > 0 else None,
         evals_executed=cat([o[5] for o in outs]) if count_executed else None,
-        start_time=cat([o[3] for o in outs]), launch_time=cat([o[4] for o in outs]))
+        start_time=cat([o[3] for o in outs]), launch_time=cat([o[4] for o in outs]),
+        lower_bound=cat([o[6].bound for o in outs]) if lower_bound else None,
+        bound_exit=cat([o[6].exit_kind for o in outs]) if lower_bound else None)
 
 
 def synthetic_model(seed=1234, device="cuda"):

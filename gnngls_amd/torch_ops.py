@@ -1,6 +1,6 @@
 """PyTorch-ROCm custom operators of the hot path: `torch.ops.gnngls.*` (north_star).
 
-Seven operators are registered with `torch.library` over the C ABI of libgnngls_hip.so (include/gnngls_hip.h).  Each has
+Eight operators are registered with `torch.library` over the C ABI of libgnngls_hip.so (include/gnngls_hip.h).  Each has
 exactly ONE implementation, for the CUDA dispatch key (= HIP on ROCm): there is no CPU kernel behind any of them, so
 calling one with CPU tensors fails in the dispatcher ("no CPU fallback" is structural, not a runtime check).  Shape
 functions (fake/meta kernels) are registered so the ops can be traced and used under FakeTensorMode.  All ops enqueue on
@@ -18,6 +18,8 @@ the current HIP stream, take caller-owned contiguous tensors and retain nothing.
     insertion(W[B,n,n] f64, depot, mode, order[B,n-1] i32 or None) -> tour[B,n+1] i32          algorithms.py:82-108
         mode in {'nearest', 'farthest', 'random'}; 'random' takes the node order (None: drawn with np.random.choice)
     cheapest_insertion(sub_tour[B,len] i32, node[B] i32, W) -> (tour[B,len+1] i32, cost[B] f64)   algorithms.py:67-79
+    one_tree_bound(D[B,n,n] f64, ub[B] f64, max_iters) -> (bound[B] f64, pi[B,n] f64, iters[B] i32, exit_kind[B] i32, status[B] i32)
+        the Held-Karp 1-tree lower bound of oracle/one_tree.c (in place of Concorde's optimum, scripts/test.py:62,104)
 """
 import ctypes
 
@@ -35,6 +37,7 @@ _LIB.define("gls_run(Tensor D, Tensor guides, Tensor init_tour, Tensor init_cost
             "-> (Tensor, Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("insertion(Tensor W, int depot, str mode, Tensor? order) -> Tensor")
 _LIB.define("cheapest_insertion(Tensor sub_tour, Tensor node, Tensor W) -> (Tensor, Tensor)")
+_LIB.define("one_tree_bound(Tensor D, Tensor ub, int max_iters) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
 
 _workspaces = {}      # device index -> uint8 scratch tensor for the forward (grown on demand, reused across calls)
 
@@ -87,6 +90,11 @@ def _gls_run(D, guides, init_tour, init_cost, perturbation_moves, max_outer_iter
     return r.best_tour, r.best_cost, r.outer_iters, trace, r.trace_len
 
 
+def _one_tree_bound(D, ub, max_iters):
+    r = ops.one_tree_bound(D, ub, max_iters=max_iters)
+    return r.bound, r.pi, r.iters, r.exit_kind, r.status
+
+
 _LIB.impl("regret_forward", _regret_forward, "CUDA")
 _LIB.impl("two_opt_delta_all", ops.two_opt_delta_all, "CUDA")
 _LIB.impl("relocate_delta_all", ops.relocate_delta_all, "CUDA")
@@ -94,6 +102,7 @@ _LIB.impl("local_search", _local_search, "CUDA")
 _LIB.impl("gls_run", _gls_run, "CUDA")
 _LIB.impl("insertion", ops.insertion, "CUDA")
 _LIB.impl("cheapest_insertion", ops.cheapest_insertion, "CUDA")
+_LIB.impl("one_tree_bound", _one_tree_bound, "CUDA")
 
 
 # ---- shape functions (fake tensors / tracing); no arithmetic -------------------------------------------------------
@@ -133,3 +142,10 @@ def _(W, depot, mode, order):
 @torch.library.register_fake("gnngls::cheapest_insertion")
 def _(sub_tour, node, W):
     return sub_tour.new_empty((sub_tour.shape[0], sub_tour.shape[1] + 1)), W.new_empty((W.shape[0],), dtype=torch.float64)
+
+
+@torch.library.register_fake("gnngls::one_tree_bound")
+def _(D, ub, max_iters):
+    B, n = D.shape[0], D.shape[1]
+    i32 = lambda: D.new_empty((B,), dtype=torch.int32)  # noqa: E731
+    return D.new_empty((B,), dtype=torch.float64), D.new_empty((B, n), dtype=torch.float64), i32(), i32(), i32()

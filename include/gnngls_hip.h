@@ -139,6 +139,38 @@ int gnngls_insertion(const double *W, int B, int n, int depot, int mode, const i
 int gnngls_cheapest_insertion(const int32_t *sub_tour, int len, const int32_t *node, const double *W, int B, int n,
                               int32_t *tour_out, double *cost_out, void *stream);
 
+/* ---- Held-Karp 1-tree lower bound of the optimal tour length (oracle/one_tree.c: one_tree_lower_bound, min_one_tree) --------
+ * The reference divides a tour's length by Concorde's optimum stored in its instance files (scripts/test.py:62,104,
+ * gnngls/__init__.py:55-60).  This entry gives the certified side this project can compute itself: for node potentials pi,
+ *      w(pi) = min over 1-trees of (c[i][j] + pi[i] + pi[j])  -  2 sum(pi)   <=   optimum,
+ * and the subgradient ascent of oracle/one_tree.c (Polyak steps towards ub, the step factor halved after `period` 1-trees
+ * without a better value: period = 25 below n = 50, else n / 2) returns max_k w(pi_k).  The kernel repeats that file's fp64
+ * operations in its order: `bound` has the bits of one_tree_lower_bound(D_b, n, ub_b, max_iters).  On uniform instances the bound
+ * lies typically 0.7-1 % below the optimum; where the ascent lands on a tour (most instances up to n ~ 20) it IS the optimum.
+ *   D         [B,n,n] fp64, finite (non-finite entries: unspecified values, every index stays in range), bitwise symmetric: an
+ *             instance whose matrix is not gets status GNNGLS_STATUS_ASYMMETRIC, bound NaN and its other outputs untouched
+ *             (one pass over the matrix before the ascent; w(pi) is a bound for symmetric costs only);
+ *   ub        [B] the length of any tour of the instance (it steers the step size only; ub <= w falls back to 1e-3 ub, or 1e-3);
+ *   max_iters >= 0, the largest number of 1-trees built (the oracle's default is 2000);
+ *   bound     [B] max_k w(pi_k) (-DBL_MAX with max_iters = 0);
+ *   pi        [B,n] or NULL: the potentials that attain it (the oracle's best_pi, which it does not return) -- the root of a
+ *             branch and bound;
+ *   iters     [B] 1-trees built;  exit_kind [B] GNNGLS_BOUND_EXIT_*;  status [B] 0 or GNNGLS_STATUS_ASYMMETRIC.
+ * One workgroup per instance and one launch for the whole batch; every loop is bounded by max_iters x n.
+ * 3 <= n <= GNNGLS_ONE_TREE_MAX_N (a larger n returns GNNGLS_ERR_UNSUPPORTED; the oracle's n < 3 branch is not reproduced).  Bad
+ * arguments are rejected on the host before any device work; B == 0 returns GNNGLS_OK. */
+#define GNNGLS_ONE_TREE_MAX_N 1024
+#define GNNGLS_BOUND_EXIT_ITERS 0     /* max_iters 1-trees were built */
+#define GNNGLS_BOUND_EXIT_STEP 1      /* the step factor fell to 1e-5 */
+#define GNNGLS_BOUND_EXIT_TOUR 2      /* the minimum 1-tree is a tour: the bound is the optimum */
+int gnngls_one_tree_bound(const double *D, const double *ub, int B, int n, int max_iters, double *bound, double *pi, int32_t *iters,
+                          int32_t *exit_kind, int32_t *status, void *stream);
+
+/* Host-side query (oracle/one_tree.c has no counterpart; scripts/bench_bounds.py reports it): the launch gnngls_one_tree_bound makes
+ * for n nodes -- *threads workgroup size (64 = one wavefront per instance, n <= 256), *lds_bytes dynamic LDS per workgroup,
+ * *nodes_per_lane register slots per lane.  Any output pointer may be NULL. */
+int gnngls_one_tree_bound_describe(int n, int *threads, int *lds_bytes, int *nodes_per_lane);
+
 /* ---- K3: guided_local_search (algorithms.py:135-195), local_search (algorithms.py:111-132) -----
  * One persistent workgroup per instance.
  *   D            [B,n,n] fp64, symmetric (it comes from nx.attr_matrix of an undirected graph) unless
@@ -366,7 +398,7 @@ enum {
     GNNGLS_PROF_GEMM_FFN1, GNNGLS_PROF_GEMM_FFN2, GNNGLS_PROF_DECISION, GNNGLS_PROF_UNPACK,
     GNNGLS_PROF_NEAREST_NEIGHBOR, GNNGLS_PROF_TOUR_COST, GNNGLS_PROF_GLS, GNNGLS_PROF_FFN_FUSED,
     GNNGLS_PROF_TRAIN_COLSUM, GNNGLS_PROF_TRAIN_ELEMENTWISE, GNNGLS_PROF_TRAIN_GEMM_BWD, GNNGLS_PROF_TRAIN_GEMM_TN,
-    GNNGLS_PROF_TRAIN_GAT_BWD, GNNGLS_PROF_INSERTION /* gnngls_insertion and gnngls_cheapest_insertion */, GNNGLS_PROF_KINDS
+    GNNGLS_PROF_TRAIN_GAT_BWD, GNNGLS_PROF_INSERTION /* gnngls_insertion and gnngls_cheapest_insertion */, GNNGLS_PROF_ONE_TREE_BOUND, GNNGLS_PROF_KINDS
 };
 int gnngls_profile_enable(int on);
 int gnngls_profile_collect(double *ms_by_kind, int64_t *launches_by_kind);

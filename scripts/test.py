@@ -7,6 +7,9 @@ on 'regret_pred' whenever that guide is used and on 'weight' otherwise (test.py:
 optimum stored in the instances) and the same DataFrame pickle (columns instance, time, opt_cost, cost, best_cost, gap,
 dt) in `run_dir/<timestamp>_<uuid>.pkl`.  `--init_tour nearest_insertion|farthest_insertion` starts from the reference's insertion
 constructors (algorithms.py:82-108) instead, `--init_weight weight` builds the start on the distances whatever the guide.
+`--lower_bound` adds the columns `lower_bound` -- the Held-Karp 1-tree bound of the instance (gnngls_amd.ops.one_tree_bound, computed
+after the search with ub = the returned cost: lower_bound <= optimum <= best_cost, certified) -- and `gap_bound` =
+(best_cost / lower_bound - 1) * 100, the gap that needs no stored optimum; without the flag the pickle has the seven columns above.
 
 Search progress (test.py:97-117).  The reference appends one row per accepted move; a 10 s TSP100 search on the GPU
 accepts ~2e6 moves per instance, i.e. ~20 GB of rows for a 1024-instance batch.  The default record here is therefore
@@ -68,6 +71,9 @@ def parse_args():
     parser.add_argument('--init_weight', type=str, default='auto', choices=['auto', 'weight'],
                         help="matrix the start tour is built on: auto = regret_pred whenever that guide is used, else weight "
                              "(test.py:70-88); weight = always the distances")
+    parser.add_argument('--lower_bound', action='store_true',
+                        help='also compute the Held-Karp 1-tree lower bound of every instance on the GPU (after its search, outside '
+                             'the budget) and write the columns lower_bound and gap_bound = (best_cost / lower_bound - 1) * 100')
     return parser.parse_args()
 
 
@@ -122,8 +128,10 @@ def default_feature_set(test_set, G):
                for e in G.edges)
 
 
-def solve_block(names, test_set, model, scalers, args, chunk, budget='per_instance'):
-    """One batch of instances -> (search-progress records, gaps), the body of the loop at test.py:59-109."""
+def solve_block(names, test_set, model, scalers, args, chunk, budget='per_instance', bound_gaps=None):
+    """One batch of instances -> (search-progress records, gaps), the body of the loop at test.py:59-109.  With --lower_bound
+    every record also carries the instance's 1-tree bound, and `bound_gaps` (a list) receives the gaps against it."""
+    want_bound = getattr(args, 'lower_bound', False)
     graphs = [datasets.read_gpickle(test_set.root_dir / name) for name in names]
     optima = [gnngls_amd.optimal_cost(G, weight='weight') for G in graphs]
     D = torch.from_numpy(np.stack([_attr_matrix(G, 'weight') for G in graphs])).cuda()
@@ -134,7 +142,8 @@ def solve_block(names, test_set, model, scalers, args, chunk, budget='per_instan
                                perturbation_moves=args.perturbation_moves, trace_cap=args.full_trace,
                                want_trace_time=args.full_trace > 0, chunk=chunk, budget=budget, imp_cap=IMP_CAP,
                                features=features, init=getattr(args, 'init_tour', 'nearest_neighbor'),
-                               init_weight=getattr(args, 'init_weight', 'auto'))
+                               init_weight=getattr(args, 'init_weight', 'auto'), lower_bound=want_bound)
+    bounds = res.lower_bound.cpu().numpy() if want_bound else None
     res.imp_cost, res.imp_time, res.imp_len = res.imp_cost.cpu(), res.imp_time.cpu(), res.imp_len.cpu()
     res.moves = res.moves.cpu()
     if args.full_trace > 0:
@@ -152,22 +161,30 @@ def solve_block(names, test_set, model, scalers, args, chunk, budget='per_instan
         # on the last iteration's cost, which may be above the best; its minimum is the best, bit for bit)
         assert rows and min(c for _, c in rows) == best[k], 'the search-progress record must reach the returned cost'
         gaps.append((best[k] / opt - 1) * 100)                                # test.py:104
+        if want_bound:
+            for r in records[-len(rows) - 1:]:
+                r['lower_bound'] = float(bounds[k])
+            if bound_gaps is not None:
+                bound_gaps.append((best[k] / bounds[k] - 1) * 100)
     if cut:
         print(f'warning: {cut} instance(s) accepted more than --full_trace {args.full_trace} moves; their rows '
               f'continue with new-best events only', file=sys.stderr)
     return records, gaps
 
 
-def records_to_array(records, n_instances, width):
+def records_to_array(records, n_instances, width, with_bound=False):
     """The records of this rank's instances (in order: a start row, then progress rows) as ONE fixed-width fp64 array
     [n_instances, 3 + 2 width]: opt_cost, start time, number of progress rows, their times, their costs (NaN padded).
-    width = --full_trace + IMP_CAP: a function of the command line alone, so every rank knows every rank's shape."""
-    out = np.full((n_instances, 3 + 2 * width), np.nan)
+    width = --full_trace + IMP_CAP: a function of the command line alone, so every rank knows every rank's shape.
+    with_bound (--lower_bound): one more column at the end, the instance's lower bound."""
+    out = np.full((n_instances, 3 + 2 * width + int(with_bound)), np.nan)
     k = -1
     for r in records:
         if 'cost' not in r:                                                   # start row of the next instance (test.py:65-68)
             k += 1
             out[k, 0], out[k, 1], out[k, 2] = r['opt_cost'], r['time'], 0
+            if with_bound:
+                out[k, -1] = r['lower_bound']
         else:
             m = int(out[k, 2])
             out[k, 3 + m], out[k, 3 + width + m] = r['time'], r['cost']
@@ -176,30 +193,31 @@ def records_to_array(records, n_instances, width):
     return out
 
 
-def array_to_records(arr, names, width):
+def array_to_records(arr, names, width, with_bound=False):
     records = []
     for row, name in zip(arr, names):
         opt = float(row[0])
-        records.append({'instance': name, 'time': float(row[1]), 'opt_cost': opt})
+        extra = {'lower_bound': float(row[-1])} if with_bound else {}
+        records.append({'instance': name, 'time': float(row[1]), 'opt_cost': opt, **extra})
         m = int(row[2])
-        records += [{'instance': name, 'opt_cost': opt, 'time': float(t), 'cost': float(c)}
+        records += [{'instance': name, 'opt_cost': opt, 'time': float(t), 'cost': float(c), **extra}
                     for t, c in zip(row[3:3 + m], row[3 + width:3 + width + m])]
     return records
 
 
-def gather_records(records, world, rank, names_all, n_local, width):
+def gather_records(records, world, rank, names_all, n_local, width, with_bound=False):
     """The one exchange of the run: a tensor `gather` of fixed-width record arrays (gnngls_amd.parallel.gather_results: shard
     sizes are a function of (total, world), no size exchange, no pickling through the collective)."""
     if not dist.is_initialized():
         return records
-    local = torch.from_numpy(records_to_array(records, n_local, width))
+    local = torch.from_numpy(records_to_array(records, n_local, width, with_bound))
     on_gpu = dist.get_backend() == 'nccl'                                     # RCCL moves device memory
     g = parallel.gather_results(local.cuda() if on_gpu else local, parallel.shard_sizes(len(names_all), world))
     dist.barrier()
     dist.destroy_process_group()
     if rank != 0:
         return None
-    return array_to_records(g.cpu().numpy(), names_all, width)
+    return array_to_records(g.cpu().numpy(), names_all, width, with_bound)
 
 
 def write_progress(records, run_dir):
@@ -209,6 +227,8 @@ def write_progress(records, run_dir):
     df['best_cost'] = by_instance['cost'].cummin()
     df['gap'] = (df['best_cost'] / df['opt_cost'] - 1) * 100
     df['dt'] = df['time'] - by_instance['time'].transform('min')
+    if 'lower_bound' in df:                                                   # --lower_bound
+        df['gap_bound'] = (df['best_cost'] / df['lower_bound'] - 1) * 100
     stamp = datetime.datetime.now().strftime('%b%d_%H-%M-%S')
     if not run_dir.exists():
         run_dir.mkdir()
@@ -225,19 +245,22 @@ def main():
     chunk = args.batch_size or max(ops.gls_resident_capacity(test_set.G.n), 1)
     lo, hi = parallel.shard_range(len(test_set.instances), world, rank)       # this rank's block of instances
     mine = test_set.instances[lo:hi]
-    records, gaps = [], []
+    records, gaps, bound_gaps = [], [], []
     block = chunk * max(args.per_batch_budget, 1)
     budget = 'per_batch' if args.per_batch_budget > 1 else 'per_instance'
     with tqdm.tqdm(total=len(mine), disable=rank != 0) as pbar:
         for start in range(0, len(mine), block):
             names = mine[start:start + block]
-            rec, g = solve_block(names, test_set, model, scalers, args, chunk, budget)
+            rec, g = solve_block(names, test_set, model, scalers, args, chunk, budget, bound_gaps)
             records += rec
             gaps += g
-            pbar.set_postfix({'Avg Gap': '{:.4f}'.format(np.mean(gaps))})
+            postfix = {'Avg Gap': '{:.4f}'.format(np.mean(gaps))}
+            if args.lower_bound:
+                postfix['Avg Gap vs Bound'] = '{:.4f}'.format(np.mean(bound_gaps))
+            pbar.set_postfix(postfix)
             pbar.update(len(names))
 
-    records = gather_records(records, world, rank, test_set.instances, len(mine), args.full_trace + IMP_CAP + 1)
+    records = gather_records(records, world, rank, test_set.instances, len(mine), args.full_trace + IMP_CAP + 1, args.lower_bound)
     if records is not None:
         write_progress(records, args.run_dir)
 
