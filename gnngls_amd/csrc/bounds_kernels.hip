@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "bounds_kernels.h"
+#include "gls_policy.h"
 
 #pragma clang fp contract(off)
 

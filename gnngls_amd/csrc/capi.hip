@@ -62,13 +62,14 @@ struct ProfScope {
 };
 
 int g_pen16_limit = 65535;
+// experiment overrides of the launch plan: they live here only and reach gls_plan() as plain fields of its request (plan_for)
 std::atomic<int> g_prune_mode{-1};     // -1 / 1 = pruned descent scans where they exist, 0 = full scans (experiments / tests)
-std::atomic<int> g_team_mode{-1};      // -1 = policy (gls_config), 0 = never, 1 = wherever the team form exists (experiments / tests)
+std::atomic<int> g_team_mode{-1};      // -1 = policy (gls_plan), 0 = never, 1 = wherever the team form exists (experiments / tests)
+std::atomic<int> g_threads_override{0};      // experiments only (gnngls_debug_set_gls_threads)
 long long *g_stamp_buffer = nullptr;
 std::atomic<long long *> g_exec_evals{nullptr};   // measurement hook (gnngls_profile_set_executed_evals)
 
-constexpr size_t kLdsPerCU = 160 * 1024;
-constexpr int kMaxWavesPerCU = 32;
+using gnngls::kLdsPerCU;
 
 int num_cus() {
     int dev = 0;
@@ -79,104 +80,43 @@ int num_cus() {
     return 256;   // MI355X
 }
 
-// Storage configuration of the persistent search kernel for instances of n nodes: the one with the
-// most resident workgroups per CU wins; ties go to the faster store (LDS penalties, 32-bit first).
-struct GlsConfig { int store; int penalty_bits; int threads; size_t lds; int per_cu; int wps; bool team = false; bool prune = false; };
+bool valid_penalty_bits(int bits) { return bits == 0 || bits == 16 || bits == 32 || bits == -1 || bits == -2; }
 
-GlsConfig gls_config_store(int n, int requested_bits, int batch, bool first_improvement);
+// the plan of a search of B instances of n nodes on the current device, under the overrides as they are now
+gnngls::GlsPlan plan_for(int n, int B, int penalty_bits, bool first_improvement, bool want_trace = false, bool want_count = false) {
+    return gnngls::gls_plan({n, B, penalty_bits, first_improvement, want_trace, want_count, num_cus(), g_team_mode.load(std::memory_order_relaxed),
+                             g_prune_mode.load(std::memory_order_relaxed), g_threads_override.load(std::memory_order_relaxed)});
+}
 
-// + the form of the perturbation phase: on all wavefronts of the workgroup (team) when every workgroup of the batch gets a
-// CU of its own (B <= number of CUs) and is a 16-wave workgroup (TSP200 x 256: one per CU by LDS anyway) -- else on
-// wavefront 0
-GlsConfig gls_config(int n, int requested_bits, int batch = 0, bool first_improvement = false) {
-    GlsConfig c = gls_config_store(n, requested_bits, batch, first_improvement);
-    const int mode = g_team_mode.load(std::memory_order_relaxed);
-    if (mode != 0 && gnngls::gls_team_supported(c.store, c.penalty_bits, c.wps, n, c.threads)) {
-        const size_t lds = gnngls::gls_lds_bytes(n, c.store, c.penalty_bits, true);
-        // ... and only for the 16-wave workgroups that own a CU by their LDS footprint (distance triangle > 80 KB: n >= 144,
-        // TSP200).  Measured (outer iterations in 2 s, team vs serial): TSP200 x 256 13.0k vs 10.9k (weight guide), 10.5k vs
-        // 10.3k (regret_pred of the synthetic model), 6.7k vs 6.8k (noise); but TSP100 x 256 on 8-wave workgroups 20.3k vs
-        // 24.2k (model guide) and TSP50 x 128 (one pass per scan) 18.3k vs 21.2k: a round's barriers, slot exchange and
-        // the re-evaluation after a move cost more than the few passes they save (profiles/r03_experiments/README.md)
-        // Round 5: the edge form of the serial phase (best improvement; gls_kernels.hip) beats the team form there too -- TSP200 x 256,
-        // outer iterations in 2 s, serial edge form vs team: 18.4k vs 15.1k (model guide), 18.8k vs 17.2k (weight) -- so the
-        // policy keeps the team form for first-improvement runs only (which have no edge form): profiles/r05_experiments/
-        const bool pays = first_improvement && batch > 0 && batch <= num_cus() && c.store == gnngls::GLS_STORE_COMPACT && c.threads == 1024;
-        if (lds <= kLdsPerCU && (mode == 1 || pays)) { c.team = true; c.lds = lds; }
+// gnngls_gls_describe_run, and with fewer outputs gnngls_gls_describe_config
+int describe_plan(const char *what, int n, int B, int penalty_bits, bool first_improvement, int *store, int *threads, int *lds_bytes,
+                  int *per_cu, int *waves_per_simd = nullptr, int *team = nullptr, int *edge_form = nullptr) {
+    if (n < 3 || B < 0 || !valid_penalty_bits(penalty_bits)) return fail(GNNGLS_ERR_ARG, "%s: bad argument", what);
+    const gnngls::GlsPlan c = plan_for(n, B, penalty_bits, first_improvement);      // exactly what gnngls_gls_run launches
+    if (c.lds > kLdsPerCU)
+        return fail(GNNGLS_ERR_UNSUPPORTED, "%s: n=%d needs %zu B of LDS for tours and edge lengths (> 160 KiB)", what, n, c.lds);
+    if (store) *store = c.store * 100 + (c.store == gnngls::GLS_STORE_TRI ? c.penalty_bits : 0);
+    if (threads) *threads = c.threads;
+    if (lds_bytes) *lds_bytes = (int)c.lds;
+    if (per_cu) *per_cu = c.store == gnngls::GLS_STORE_GLOBAL ? 0 : c.per_cu;
+    if (waves_per_simd) *waves_per_simd = c.wps;
+    if (team) *team = c.team ? 1 : 0;
+    if (edge_form) *edge_form = c.edge_form ? 1 : 0;
+    return GNNGLS_OK;
+}
+
+// stream-ordered scratch: freed on the stream it was allocated on when the scope ends, behind what the scope enqueued
+struct StreamScratch {
+    void *p = nullptr; hipStream_t st;
+    explicit StreamScratch(hipStream_t s) : st(s) {}
+    StreamScratch(const StreamScratch &) = delete;
+    ~StreamScratch() { if (p) (void)hipFreeAsync(p, st); }
+    hipError_t alloc(size_t bytes) {
+        const hipError_t e = hipMallocAsync(&p, bytes, st);
+        if (e != hipSuccess) p = nullptr;
+        return e;
     }
-    return c;
-}
-
-// + the pruned descent scans (nearest-neighbour lists: 2-opt scan from n = 80, relocate scan from n = 128; the position table
-// sits in the LDS slot the best tour used to have, so the footprint does not change)
-GlsConfig gls_config_run(int n, int requested_bits, int batch, bool first_improvement) {
-    GlsConfig c = gls_config(n, requested_bits, batch, first_improvement);
-    c.prune = g_prune_mode.load(std::memory_order_relaxed) != 0 && gnngls::gls_prune_supported(c.store, n, first_improvement, c.wps);
-    return c;
-}
-
-GlsConfig gls_config_store(int n, int requested_bits, int batch, bool first_improvement) {
-    GlsConfig pick{gnngls::GLS_STORE_GLOBAL, 32, gnngls::gls_block_threads(n, gnngls::GLS_STORE_GLOBAL),
-                   gnngls::gls_lds_bytes(n, gnngls::GLS_STORE_GLOBAL, 32), 0, 4};
-    bool have = false, done = false;
-    const int cus = num_cus();
-    // candidates are visited fastest store first (LDS penalties 32-bit, LDS penalties 16-bit, compact); the first one
-    // that keeps the whole batch resident wins, otherwise the one with the most resident workgroups per CU
-    auto by_lds_of = [](size_t lds) { return (int)(kLdsPerCU / lds); };
-    auto consider = [&](int store, int bits) {
-        if (done) return;
-        size_t lds = gnngls::gls_lds_bytes(n, store, bits);
-        if (lds > kLdsPerCU) return;
-        // single-wavefront workgroups for n <= 33 only where the half-wave descent scans exist: best improvement, 128-VGPR build
-        int threads = gnngls::gls_block_threads(n, store, bits, !first_improvement);
-        // compact store, batch larger than the 128-VGPR build keeps resident at the default workgroup size: halve the
-        // workgroup (down to the wavefronts the lean scans need, one per block of 64 rows) before falling back to the
-        // 64-VGPR build -- TSP50 x 2048 on 2-wave workgroups at 128 VGPRs: 6.2k outer iterations per second vs 5.6k on
-        // 4-wave workgroups at 64 VGPRs (profiles/r02_ab_small_n_threads.log)
-        if (store == gnngls::GLS_STORE_COMPACT && batch > 0) {
-            const int by_lds = (int)(kLdsPerCU / lds);
-            const int min_threads = 64 * ((n - 1 + 63) / 64);
-            while (threads > min_threads && threads > 64) {
-                const int per4 = by_lds < 16 / (threads / 64) ? by_lds : 16 / (threads / 64);
-                if ((long)per4 * cus >= batch || per4 == by_lds) break;
-                threads /= 2;
-            }
-        }
-        // wave slots per CU at the register budget of the kernel instantiation: LDS-penalty stores 80 VGPRs -> 6 waves
-        // per SIMD (24 per CU); compact store 128 VGPRs -> 4 per SIMD, or its 64-VGPR build -> 8 per SIMD when only that
-        // keeps the batch resident (and, without a batch size, for the capacity query)
-        int wps = gnngls::gls_waves_per_simd(store, n, batch, cus, threads, lds);
-        if (store == gnngls::GLS_STORE_COMPACT && batch <= 0) wps = 8;
-        if (store == gnngls::GLS_STORE_TRI && bits == 16) wps = 6;            // the uint16 variant only exists as the 80-VGPR build
-        // (n = 25..33 beyond the 128-VGPR residency end up on the 64-VGPR build, which has no half-wave scans, still as ONE
-        // wavefront per instance: measured TSP30 x 8192, 1 s -- 64 threads keep all 8192 resident, 6.2k iterations each;
-        // 128 threads halve the residency: 8.8k iterations each in two rounds of 1 s, half the aggregate rate
-        // (profiles/r04_ab_threads_tsp30x8192.log))
-        // batches of at most two single-wavefront workgroups per SIMD: the 256-VGPR build of the one-slot kernel
-        // (not while the test hook forces the team form, which only exists on the 128-VGPR build)
-        if (wps == 4 && batch > 0 && g_team_mode.load(std::memory_order_relaxed) != 1 &&
-            gnngls::gls_wps2_supported(store, bits, n, threads, first_improvement)) {
-            const int per2 = by_lds_of(lds) < 8 ? by_lds_of(lds) : 8;
-            if ((long)per2 * cus >= batch) wps = 2;
-        }
-        const int by_waves = (wps * 4) / (threads / 64);
-        int per_cu = (int)(kLdsPerCU / lds);
-        if (per_cu > by_waves) per_cu = by_waves;
-        if (!have || per_cu > pick.per_cu) { pick = GlsConfig{store, bits, threads, lds, per_cu, wps}; have = true; }
-        if (batch > 0 && (long)per_cu * cus >= batch) { pick = GlsConfig{store, bits, threads, lds, per_cu, wps}; done = true; }
-    };
-    if (requested_bits == -2) {               // forced compact store (falls through to the global store if it cannot fit)
-        if (n <= 255) consider(gnngls::GLS_STORE_COMPACT, 32);
-        return pick;
-    }
-    if (requested_bits < 0) return pick;      // forced global-memory store (exact index order, asymmetric D allowed)
-    if (requested_bits == 0 || requested_bits == 32) consider(gnngls::GLS_STORE_TRI, 32);
-    // 16-bit LDS counters only on request: they overflow within a 10 s run when an uninformative guide
-    // concentrates the penalties on a few edges, and an overflow costs a whole rerun of that instance
-    if (requested_bits == 16) consider(gnngls::GLS_STORE_TRI, 16);
-    if (requested_bits == 0 && n <= 255) consider(gnngls::GLS_STORE_COMPACT, 32);
-    return pick;
-}
+};
 }  // namespace
 
 extern "C" {
@@ -186,65 +126,35 @@ const char *gnngls_last_error(void) { return g_err; }
 
 int gnngls_gls_resident_capacity(int n) {
     if (n < 3) return 0;
-    GlsConfig c = gls_config(n, 0);
+    const gnngls::GlsPlan c = plan_for(n, 0, 0, false);
     if (c.store == gnngls::GLS_STORE_GLOBAL) return 0;
     return c.per_cu * num_cus();
 }
 
 int gnngls_gls_describe_config(int n, int B, int penalty_bits, int *store, int *threads, int *lds_bytes, int *per_cu) {
-    if (n < 3 || B < 0 || (penalty_bits != 0 && penalty_bits != 16 && penalty_bits != 32 && penalty_bits != -1 && penalty_bits != -2))
-        return fail(GNNGLS_ERR_ARG, "gls_describe_config: bad argument");
-    const GlsConfig c = gls_config_run(n, penalty_bits, B, false);     // as a best-improvement run would be launched
-    if (c.lds > kLdsPerCU)
-        return fail(GNNGLS_ERR_UNSUPPORTED, "gls_describe_config: n=%d needs %zu B of LDS for tours and edge lengths (> 160 KiB)", n, c.lds);
-    if (store) *store = c.store * 100 + (c.store == gnngls::GLS_STORE_TRI ? c.penalty_bits : 0);
-    if (threads) *threads = c.threads;
-    if (lds_bytes) *lds_bytes = (int)c.lds;
-    if (per_cu) *per_cu = c.store == gnngls::GLS_STORE_GLOBAL ? 0 : c.per_cu;
-    return GNNGLS_OK;
+    return describe_plan("gls_describe_config", n, B, penalty_bits, false, store, threads, lds_bytes, per_cu);     // as a best-improvement run would be launched
 }
 
 int gnngls_gls_describe_run(int n, int B, int penalty_bits, int first_improvement, int *store, int *threads, int *lds_bytes,
                             int *per_cu, int *waves_per_simd, int *team, int *edge_form) {
-    if (n < 3 || B < 0 || (penalty_bits != 0 && penalty_bits != 16 && penalty_bits != 32 && penalty_bits != -1 && penalty_bits != -2))
-        return fail(GNNGLS_ERR_ARG, "gls_describe_run: bad argument");
-    const GlsConfig c = gls_config_run(n, penalty_bits, B, first_improvement != 0);      // exactly what gnngls_gls_run launches
-    if (c.lds > kLdsPerCU)
-        return fail(GNNGLS_ERR_UNSUPPORTED, "gls_describe_run: n=%d needs %zu B of LDS for tours and edge lengths (> 160 KiB)", n, c.lds);
-    if (store) *store = c.store * 100 + (c.store == gnngls::GLS_STORE_TRI ? c.penalty_bits : 0);
-    if (threads) *threads = c.threads;
-    if (lds_bytes) *lds_bytes = (int)c.lds;
-    if (per_cu) *per_cu = c.store == gnngls::GLS_STORE_GLOBAL ? 0 : c.per_cu;
-    if (waves_per_simd) *waves_per_simd = c.wps;
-    if (team) *team = c.team ? 1 : 0;
-    if (edge_form) *edge_form = gnngls::gls_edge_form(c.store, c.penalty_bits, c.wps, c.team, first_improvement != 0) ? 1 : 0;
-    return GNNGLS_OK;
+    return describe_plan("gls_describe_run", n, B, penalty_bits, first_improvement != 0, store, threads, lds_bytes, per_cu, waves_per_simd,
+                         team, edge_form);
 }
 
 int gnngls_gls_kernel_resources(int n, int B, int penalty_bits, int first_improvement, int trace, int *vgprs, int *scratch_bytes) {
-    if (n < 3 || B < 0 || (penalty_bits != 0 && penalty_bits != 16 && penalty_bits != 32 && penalty_bits != -1 && penalty_bits != -2))
-        return fail(GNNGLS_ERR_ARG, "gls_kernel_resources: bad argument");
-    const GlsConfig c = gls_config_run(n, penalty_bits, B, first_improvement != 0);
-    gnngls::GlsArgs A;
-    memset(&A, 0, sizeof(A));
-    A.n = n; A.B = B;
-    static double dummy;
-    if (trace) { A.trace_cap = 1; A.trace_cost = &dummy; }                     // (selects the tracing instantiation; never dereferenced)
-    if (c.prune) { A.nl_id = reinterpret_cast<const uint8_t *>(&dummy); }     // (likewise)
-    const hipError_t e = gnngls::gls_kernel_resources(A, c.store, c.penalty_bits, c.threads, c.wps, c.team, first_improvement != 0, vgprs, scratch_bytes);
+    if (n < 3 || B < 0 || !valid_penalty_bits(penalty_bits)) return fail(GNNGLS_ERR_ARG, "gls_kernel_resources: bad argument");
+    const hipError_t e = gnngls::gls_kernel_resources(plan_for(n, B, penalty_bits, first_improvement != 0, trace != 0), vgprs, scratch_bytes);
     return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "gls_kernel_resources");
 }
 
 int gnngls_gls_waves_per_simd(int n, int B, int penalty_bits) {
-    if (n < 3 || B < 0 || (penalty_bits != 0 && penalty_bits != 16 && penalty_bits != 32 && penalty_bits != -1 && penalty_bits != -2))
-        return 0;
-    return gls_config(n, penalty_bits, B).wps;
+    if (n < 3 || B < 0 || !valid_penalty_bits(penalty_bits)) return 0;
+    return plan_for(n, B, penalty_bits, false).wps;
 }
 
 int gnngls_gls_uses_team(int n, int B, int penalty_bits) {
-    if (n < 3 || B < 0 || (penalty_bits != 0 && penalty_bits != 16 && penalty_bits != 32 && penalty_bits != -1 && penalty_bits != -2))
-        return 0;
-    return gls_config(n, penalty_bits, B).team ? 1 : 0;
+    if (n < 3 || B < 0 || !valid_penalty_bits(penalty_bits)) return 0;
+    return plan_for(n, B, penalty_bits, false).team ? 1 : 0;
 }
 
 int gnngls_two_opt_delta_all(const int32_t *tour, const double *D, int B, int n, double *out, void *stream) {
@@ -266,7 +176,8 @@ int gnngls_best_move(const int32_t *tour, const double *D, int B, int n, int op,
     if (B == 0) return GNNGLS_OK;   // empty batch: nothing to enqueue (data pointers may be NULL)
     if (!tour || !D || !delta_out || !move_out || B < 0 || n < 3 || (op != 0 && op != 1) || n > 65535)
         return fail(GNNGLS_ERR_ARG, "best_move: bad argument");
-    hipError_t e = gnngls::launch_best_move(tour, D, B, n, op, pos_i, first_improvement != 0, delta_out, move_out,
+    const int threads = gnngls::gls_block_threads(n, gnngls::GLS_STORE_GLOBAL, 32, true, g_threads_override.load(std::memory_order_relaxed));
+    hipError_t e = gnngls::launch_best_move(tour, D, B, n, op, pos_i, first_improvement != 0, threads, delta_out, move_out,
                                             new_tour, (hipStream_t)stream);
     return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "best_move");
 }
@@ -370,7 +281,7 @@ int gnngls_gls_run(const double *D, const double *guides, int n_guides, int B, i
     if (max_outer_iters != 0 && (!guides || n_guides < 1))
         return fail(GNNGLS_ERR_ARG, "gls_run: guides required when outer iterations are requested");
     if (!(watchdog_s > 0.0)) return fail(GNNGLS_ERR_ARG, "gls_run: watchdog_s must be > 0");
-    if (penalty_bits != 0 && penalty_bits != 16 && penalty_bits != 32 && penalty_bits != -1 && penalty_bits != -2)
+    if (!valid_penalty_bits(penalty_bits))
         return fail(GNNGLS_ERR_ARG, "gls_run: penalty_bits must be 0 (auto), 16, 32, -1 (global-memory store) or -2 (compact store)");
     hipStream_t st = (hipStream_t)stream;
     gnngls::GlsArgs A;
@@ -386,10 +297,11 @@ int gnngls_gls_run(const double *D, const double *guides, int n_guides, int B, i
     A.stamps = g_stamp_buffer;
     A.evals_exec = g_exec_evals.load(std::memory_order_relaxed);
     A.trace_len = trace_len; A.penalty_out = penalty_out; A.evals = (long long *)evals_out; A.status = status;
-    const GlsConfig cfg = gls_config_run(n, penalty_bits, B, first_improvement != 0);
+    const gnngls::GlsPlan cfg = plan_for(n, B, penalty_bits, first_improvement != 0, A.trace_cap > 0, A.evals_exec != nullptr);
     if (cfg.lds > kLdsPerCU)     // even the global-memory store keeps tours and per-position edge lengths in LDS
         return fail(GNNGLS_ERR_UNSUPPORTED, "gls_run: n=%d needs %zu B of LDS for tours and edge lengths (> 160 KiB)", n, cfg.lds);
-    int32_t *ws = nullptr;
+    StreamScratch ws(st), asym(st), nl(st);      // freed behind the launch: neighbour lists, asymmetry flags, penalty workspace
+    hipError_t e;
     if (cfg.store != gnngls::GLS_STORE_TRI) {
         // penalties in global memory (zeroed workspace): full matrices for the global store, packed
         // triangles for the compact store
@@ -397,46 +309,40 @@ int gnngls_gls_run(const double *D, const double *guides, int n_guides, int B, i
         // (the team form of the compact store keeps a full symmetric matrix too: row-contiguous reads, see TriDGlobalPF)
         size_t per = (cfg.store == gnngls::GLS_STORE_GLOBAL || cfg.team) ? (size_t)n * n : (size_t)n * (n - 1) / 2;
         size_t bytes = (size_t)B * per * sizeof(int32_t);
-        hipError_t e = hipMallocAsync((void **)&ws, bytes, st);
+        e = ws.alloc(bytes);
         if (e != hipSuccess) return hip_fail(e, "gls_run: workspace alloc");
-        e = hipMemsetAsync(ws, 0, bytes, st);
+        e = hipMemsetAsync(ws.p, 0, bytes, st);
         if (e != hipSuccess) return hip_fail(e, "gls_run: workspace memset");
-        A.pen_ws = ws;
+        A.pen_ws = (int32_t *)ws.p;
     }
-    hipError_t e;
     if (A.evals_exec) {          // the wavefronts of an instance add their counts atomically
         // a run that prunes on an instantiation without the counting code cannot report the executed evaluations: -1
-        const bool unknown = cfg.prune && !gnngls::gls_count_supported(cfg.store, cfg.wps, n, first_improvement != 0, A.trace_cap > 0);
         e = hipMemsetAsync(A.evals_exec, 0, (size_t)GNNGLS_EXEC_RECORDS * B * sizeof(long long), st);       // counts + the cycle records
-        if (e == hipSuccess && unknown) e = hipMemsetAsync(A.evals_exec, 0xff, (size_t)B * sizeof(long long), st);
-        if (e != hipSuccess) { if (ws) (void)hipFreeAsync(ws, st); return hip_fail(e, "gls_run: executed-evaluations buffer"); }
-        if (unknown) A.evals_exec = nullptr;
+        if (e == hipSuccess && cfg.count_unknown) e = hipMemsetAsync(A.evals_exec, 0xff, (size_t)B * sizeof(long long), st);
+        if (e != hipSuccess) return hip_fail(e, "gls_run: executed-evaluations buffer");
+        if (cfg.count_unknown) A.evals_exec = nullptr;
     }
-    int32_t *asym = nullptr;     // symmetric stores keep D[max, min] only: instances with an asymmetric matrix are flagged, not searched
+    // symmetric stores keep D[max, min] only: instances with an asymmetric matrix are flagged, not searched
     if (cfg.store != gnngls::GLS_STORE_GLOBAL) {
-        e = hipMallocAsync((void **)&asym, (size_t)B * sizeof(int32_t), st);
-        if (e == hipSuccess) e = gnngls::launch_symmetry_check(D, B, n, asym, st);
-        if (e != hipSuccess) { if (asym) (void)hipFreeAsync(asym, st); if (ws) (void)hipFreeAsync(ws, st); return hip_fail(e, "gls_run: symmetry check"); }
-        A.asym = asym;
+        e = asym.alloc((size_t)B * sizeof(int32_t));
+        if (e == hipSuccess) e = gnngls::launch_symmetry_check(D, B, n, (int32_t *)asym.p, st);
+        if (e != hipSuccess) return hip_fail(e, "gls_run: symmetry check");
+        A.asym = (int32_t *)asym.p;
     }
-    void *nl = nullptr;          // nearest-neighbour lists of the pruned descent scans
-    if (cfg.prune) {
+    if (cfg.prune) {             // nearest-neighbour lists of the pruned descent scans
         const size_t entries = (size_t)B * n * gnngls::kNeighborListLen;
-        e = hipMallocAsync(&nl, (size_t)B * sizeof(int32_t) + entries, st);
-        if (e != hipSuccess) { if (asym) (void)hipFreeAsync(asym, st); if (ws) (void)hipFreeAsync(ws, st); return hip_fail(e, "gls_run: neighbour-list alloc"); }
-        int32_t *ok = (int32_t *)nl;
+        e = nl.alloc((size_t)B * sizeof(int32_t) + entries);
+        if (e != hipSuccess) return hip_fail(e, "gls_run: neighbour-list alloc");
+        int32_t *ok = (int32_t *)nl.p;
         uint8_t *nl_id = (uint8_t *)(ok + B);
         e = gnngls::launch_neighbor_lists(D, B, n, nl_id, ok, st);
-        if (e != hipSuccess) { (void)hipFreeAsync(nl, st); if (asym) (void)hipFreeAsync(asym, st); if (ws) (void)hipFreeAsync(ws, st); return hip_fail(e, "gls_run: neighbour lists"); }
+        if (e != hipSuccess) return hip_fail(e, "gls_run: neighbour lists");
         A.nl_id = nl_id; A.prune_ok = ok;
     }
     {
         ProfScope ps(GNNGLS_PROF_GLS, st);
-        e = gnngls::launch_gls(A, cfg.store, cfg.penalty_bits, cfg.threads, cfg.wps, cfg.team, first_improvement != 0, st);
+        e = gnngls::launch_gls(A, cfg, st);
     }
-    if (nl) (void)hipFreeAsync(nl, st);
-    if (asym) (void)hipFreeAsync(asym, st);
-    if (ws) (void)hipFreeAsync(ws, st);
     return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "gls_run");
 }
 
@@ -460,17 +366,16 @@ int gnngls_regret_labels(const double *D, int B, int n, const int32_t *base_tour
         return fail(GNNGLS_ERR_ARG, "regret_labels: max_outer_iters must be >= 0 (labels are defined by an iteration count)");
     if (perturbation_moves < 0) return fail(GNNGLS_ERR_ARG, "regret_labels: perturbation_moves must be >= 0");
     if (!(watchdog_s > 0.0)) return fail(GNNGLS_ERR_ARG, "regret_labels: watchdog_s must be > 0");
-    if (penalty_bits != 0 && penalty_bits != 16 && penalty_bits != 32 && penalty_bits != -1 && penalty_bits != -2)
+    if (!valid_penalty_bits(penalty_bits))
         return fail(GNNGLS_ERR_ARG, "regret_labels: penalty_bits must be 0 (auto), 16, 32, -1 or -2");
     if (chunk_jobs < 0) return fail(GNNGLS_ERR_ARG, "regret_labels: chunk_jobs must be >= 0 (0 = gnngls_regret_labels_chunk(n))");
     hipStream_t st = (hipStream_t)stream;
     const int n1 = n + 1, N = n * (n - 1) / 2;
     // small per-instance workspace: M_b, base cost, rank of the best tour, asymmetry flags
-    char *ws = nullptr;
-    const size_t ws_bytes = (size_t)B * (3 * sizeof(double) + 2 * sizeof(int32_t));
-    hipError_t e = hipMallocAsync((void **)&ws, ws_bytes, st);
+    StreamScratch ws(st), cw(st);        // (the per-chunk workspace below: freed first)
+    hipError_t e = ws.alloc((size_t)B * (3 * sizeof(double) + 2 * sizeof(int32_t)));
     if (e != hipSuccess) return hip_fail(e, "regret_labels: workspace alloc");
-    double *offset = (double *)ws, *base_cost = offset + B;
+    double *offset = (double *)ws.p, *base_cost = offset + B;
     int32_t *best_rank = (int32_t *)(base_cost + 2 * B), *asym = best_rank + B;
     // the host builds the job lists: it needs the base tours (validated here) and the mask; an asymmetric D is rejected
     std::vector<int32_t> tours_h((size_t)B * n1), asym_h(B);
@@ -480,7 +385,7 @@ int gnngls_regret_labels(const double *D, int B, int n, const int32_t *base_tour
     if (e == hipSuccess) e = hipMemcpyAsync(tours_h.data(), base_tour, tours_h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && edge_mask) e = hipMemcpyAsync(mask_h.data(), edge_mask, mask_h.size(), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipFreeAsync(ws, st); return hip_fail(e, "regret_labels: reading the base tours"); }
+    if (e != hipSuccess) return hip_fail(e, "regret_labels: reading the base tours");
     std::vector<int32_t> pos((size_t)B * n);
     for (int b = 0; b < B; ++b) {
         const int32_t *t = &tours_h[(size_t)b * n1];
@@ -491,18 +396,15 @@ int gnngls_regret_labels(const double *D, int B, int n, const int32_t *base_tour
             ok = t[p] >= 0 && t[p] < n && pb[t[p]] < 0;
             if (ok) pb[t[p]] = p;
         }
-        if (!ok) { (void)hipFreeAsync(ws, st); return fail(GNNGLS_ERR_ARG, "regret_labels: base_tour[%d] is not a tour from depot 0", b); }
-        if (asym_h[b]) {
-            (void)hipFreeAsync(ws, st);
-            return fail(GNNGLS_ERR_ARG, "regret_labels: D[%d] is not symmetric (a fixed edge is an undirected edge)", b);
-        }
+        if (!ok) return fail(GNNGLS_ERR_ARG, "regret_labels: base_tour[%d] is not a tour from depot 0", b);
+        if (asym_h[b]) return fail(GNNGLS_ERR_ARG, "regret_labels: D[%d] is not symmetric (a fixed edge is an undirected edge)", b);
     }
     e = gnngls::launch_label_offsets(D, B, n, offset, st);
     if (e == hipSuccess) e = gnngls::launch_tour_cost(base_tour, D, B, n, base_cost, st);
     if (e == hipSuccess)
         e = gnngls::launch_label_init(B, n, base_tour, base_cost, edge_mask != nullptr, edge_cost, best_cost, best_rank, best_tour,
                                       status, st);
-    if (e != hipSuccess) { (void)hipFreeAsync(ws, st); return hip_fail(e, "regret_labels: init"); }
+    if (e != hipSuccess) return hip_fail(e, "regret_labels: init");
 
     // per-chunk workspace: jobs, D' (= the guide), start and returned tours, costs, search status
     long total = 0;                                     // fixed-edge jobs of this call
@@ -516,21 +418,18 @@ int gnngls_regret_labels(const double *D, int B, int n, const int32_t *base_tour
     }
     if (total == 0) {
         e = gnngls::launch_label_finalize(B, n, base_tour, base_cost, edge_cost, regret, st);
-        (void)hipFreeAsync(ws, st);
         return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "regret_labels: finalize");
     }
     int J = chunk_jobs > 0 ? chunk_jobs : gnngls_regret_labels_chunk(n);
     if (J > total) J = (int)total;
-    char *cw = nullptr;
     const size_t dp_bytes = (size_t)J * n * n * sizeof(double);
     const size_t cw_bytes = dp_bytes + (size_t)J * (sizeof(gnngls::LabelJob) + 2 * n1 * sizeof(int32_t) + 3 * sizeof(double) +
                                                     sizeof(int32_t));
-    e = hipMallocAsync((void **)&cw, cw_bytes, st);
-    if (e != hipSuccess) { (void)hipFreeAsync(ws, st); return hip_fail(e, "regret_labels: chunk workspace alloc"); }
-    double *Dp = (double *)cw, *init_cost = Dp + (size_t)J * n * n, *search_cost = init_cost + J, *job_cost = search_cost + J;
+    e = cw.alloc(cw_bytes);
+    if (e != hipSuccess) return hip_fail(e, "regret_labels: chunk workspace alloc");
+    double *Dp = (double *)cw.p, *init_cost = Dp + (size_t)J * n * n, *search_cost = init_cost + J, *job_cost = search_cost + J;
     gnngls::LabelJob *jobs_d = (gnngls::LabelJob *)(job_cost + J);
     int32_t *tin = (int32_t *)(jobs_d + J), *tout = tin + (size_t)J * n1, *job_status = tout + (size_t)J * n1;
-    auto release = [&]() { (void)hipFreeAsync(cw, st); (void)hipFreeAsync(ws, st); };
 
     // one chunk: expand, search, collect; then (16-bit counters) rerun the jobs that overflowed with 32-bit counters
     std::vector<int32_t> status_h(J);
@@ -568,17 +467,16 @@ int gnngls_regret_labels(const double *D, int B, int n, const int32_t *base_tour
                 chunk.push_back(gnngls::LabelJob{b, i, j, r});
                 if ((int)chunk.size() == J) {
                     const int rc = run(chunk, penalty_bits);
-                    if (rc != GNNGLS_OK) { release(); return rc; }
+                    if (rc != GNNGLS_OK) return rc;
                     chunk.clear();
                 }
             }
     }
     if (!chunk.empty()) {
         const int rc = run(chunk, penalty_bits);
-        if (rc != GNNGLS_OK) { release(); return rc; }
+        if (rc != GNNGLS_OK) return rc;
     }
     e = gnngls::launch_label_finalize(B, n, base_tour, base_cost, edge_cost, regret, st);
-    release();
     return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "regret_labels: finalize");
 }
 
@@ -589,6 +487,18 @@ int gnngls_regret_labels(const double *D, int B, int n, const int32_t *base_tour
 // ---------------------------------------------------------------------------------------------
 namespace {
 constexpr long kLayerFloats = 128L * 128 + 128 + 128 + 128 + 128 + 512L * 128 + 512 + 128L * 512 + 128 + 128 + 128;
+// the parameters of one layer inside the packed weights (and, with T = float, of their gradients): models.py:20-36
+template <typename T>
+struct LayerParams { T *fc_w, *attn_l, *attn_r, *bn1_g, *bn1_b, *w1, *b1, *w2, *b2, *bn2_g, *bn2_b; };
+template <typename T>
+LayerParams<T> layer_params(T *w) {
+    LayerParams<T> p;
+    p.fc_w = w; p.attn_l = p.fc_w + 128L * 128; p.attn_r = p.attn_l + 128; p.bn1_g = p.attn_r + 128; p.bn1_b = p.bn1_g + 128;
+    p.w1 = p.bn1_b + 128; p.b1 = p.w1 + 512L * 128; p.w2 = p.b1 + 512; p.b2 = p.w2 + 128L * 512; p.bn2_g = p.b2 + 128; p.bn2_b = p.bn2_g + 128;
+    return p;
+}
+#define GNNGLS_TRY(x) do { e = (x); if (e != hipSuccess) return hip_fail(e, #x); } while (0)
+
 constexpr long kBytesPerNode = (128 + 128 + 256 + 32 + 128) * 4L;   // h, ft, part, part_ms, h2 (ping-pong)
 // 16 heads: + the per-head softmax statistics of both sides [2][16 + 16] (gat_heads_merge16_kernel's input)
 long bytes_per_node(int n_heads) { return kBytesPerNode + (n_heads == 16 ? 2 * 32 * 4L : 0); }
@@ -596,10 +506,6 @@ long bytes_per_node(int n_heads) { return kBytesPerNode + (n_heads == 16 ? 2 * 3
 int heads_fail(const char *what, int n_heads) {
     return fail(GNNGLS_ERR_UNSUPPORTED, "%s: n_heads=%d is not supported (embed_dim 128: n_heads in {1, 2, 4, 8, 16})", what, n_heads);
 }
-
-int forward_prepared_impl(const float *feat, const float *weights, const void *prepared, int64_t prepared_bytes, int B, int n,
-                          int in_dim, int n_layers, int n_heads, float *y_out, void *workspace, int64_t workspace_bytes,
-                          void *stream);
 }  // namespace
 
 extern "C" {
@@ -609,11 +515,7 @@ int64_t gnngls_model_packed_floats(int in_dim, int n_layers) {
     return 128L * in_dim + 128 + (long)n_layers * kLayerFloats + 128 + 4;
 }
 
-int64_t gnngls_regret_forward_workspace_bytes(int B, int n) {
-    if (B < 1 || n < 2 || n > 65535) return 0;          // 65535 nodes x 2^31 instances still fits an int64
-    long N = (long)n * (n - 1) / 2;
-    return (int64_t)B * N * kBytesPerNode + 256;
-}
+int64_t gnngls_regret_forward_workspace_bytes(int B, int n) { return gnngls_regret_forward_workspace_bytes_heads(B, n, 8); }
 
 int64_t gnngls_regret_prepared_bytes(int n_layers) {
     if (n_layers < 0) return 0;
@@ -629,25 +531,18 @@ int gnngls_regret_prepare(const float *weights, int in_dim, int n_layers, void *
     unsigned char *base = (unsigned char *)(((uintptr_t)prepared + 255) & ~(uintptr_t)255);
     const float *layers = weights + 128L * in_dim + 128;
     for (int l = 0; l < n_layers; ++l) {
-        const float *w = layers + (long)l * kLayerFloats;
-        const float *w1 = w + 128L * 128 + 4 * 128, *w2 = w1 + 512L * 128 + 512;
+        const LayerParams<const float> p = layer_params(layers + (long)l * kLayerFloats);
         const float *fc_next = l + 1 < n_layers ? layers + (long)(l + 1) * kLayerFloats : nullptr;
-        hipError_t e = gnngls::launch_ffn_pack(w1, w2, fc_next, base + (size_t)l * gnngls::ffn_packed_bytes(), (hipStream_t)stream);
+        hipError_t e = gnngls::launch_ffn_pack(p.w1, p.w2, fc_next, base + (size_t)l * gnngls::ffn_packed_bytes(), (hipStream_t)stream);
         if (e != hipSuccess) return hip_fail(e, "regret_prepare");
     }
     if (n_layers > 0 && in_dim <= gnngls::embed_fc_max_in_dim()) {
-        hipError_t e = gnngls::launch_embed_fc_prepare(weights, weights + 128L * in_dim, layers, layers + 128L * 128, layers + 128L * 128 + 128,
+        const LayerParams<const float> p = layer_params(layers);
+        hipError_t e = gnngls::launch_embed_fc_prepare(weights, weights + 128L * in_dim, p.fc_w, p.attn_l, p.attn_r,
                                                        in_dim, base + (size_t)n_layers * gnngls::ffn_packed_bytes(), (hipStream_t)stream);
         if (e != hipSuccess) return hip_fail(e, "regret_prepare");
     }
     return GNNGLS_OK;
-}
-
-int gnngls_regret_forward_prepared(const float *feat, const float *weights, const void *prepared, int64_t prepared_bytes,
-                                   int B, int n, int in_dim, int n_layers,
-                                   float *y_out, void *workspace, int64_t workspace_bytes, void *stream) {
-    return forward_prepared_impl(feat, weights, prepared, prepared_bytes, B, n, in_dim, n_layers, 8, y_out, workspace, workspace_bytes,
-                                 stream);
 }
 
 }  // extern "C"
@@ -692,7 +587,6 @@ int forward_prepared_impl(const float *feat, const float *weights, const void *p
     const float *layers = emb_b + 128;
     const float *dec_w = layers + (long)n_layers * kLayerFloats, *dec_b = dec_w + 128;
     hipError_t e = hipSuccess;
-#define GNNGLS_TRY(x) do { e = (x); if (e != hipSuccess) return hip_fail(e, #x); } while (0)
     for (long b0 = 0; b0 < B; b0 += Bc) {
         const int bc = (int)((B - b0) < Bc ? (B - b0) : Bc);
         const long M = (long)bc * N;
@@ -711,32 +605,28 @@ int forward_prepared_impl(const float *feat, const float *weights, const void *p
                                                             rank1_gat0 ? nullptr : ft, M, in_dim, st));
           else GNNGLS_TRY(gnngls::launch_embed(feat + b0 * N * in_dim, emb_w, emb_b, h, M, in_dim, st)); }
         for (int l = 0; l < n_layers; ++l) {                                                          // models.py:67-68
-            const float *w = layers + (long)l * kLayerFloats;
-            const float *fc_w = w, *attn_l = fc_w + 128L * 128, *attn_r = attn_l + 128;
-            const float *bn1_s = attn_r + 128, *bn1_b = bn1_s + 128;
-            const float *w1 = bn1_b + 128, *b1 = w1 + 512L * 128, *w2 = b1 + 512, *b2 = w2 + 128L * 512;
-            const float *bn2_s = b2 + 128, *bn2_b = bn2_s + 128;
+            const LayerParams<const float> p = layer_params(layers + (long)l * kLayerFloats);
             // ft = fc(h), models.py:23: a launch of its own for the first layer (and for every layer on the fp32 path); on the bf16x3 path
             // the feed-forward launch of layer l - 1 has already written it (fc folded into that kernel's tail)
             if ((l == 0 && !fused_fc0) || !prep) {
               ProfScope ps(GNNGLS_PROF_GEMM_FC, st);
-              GNNGLS_TRY(gnngls::launch_gemm(gnngls::GEMM_EPI_STORE, h, fc_w, ft, M, 128, 128, nullptr, nullptr, nullptr, nullptr, st)); }
+              GNNGLS_TRY(gnngls::launch_gemm(gnngls::GEMM_EPI_STORE, h, p.fc_w, ft, M, 128, 128, nullptr, nullptr, nullptr, nullptr, st)); }
             if (l == 0 && rank1_gat0) {
               ProfScope ps(GNNGLS_PROF_GAT_ROWS_RANK1, st);
               GNNGLS_TRY(gnngls::launch_gat_rows_rank1(feat + b0 * N, prep + (size_t)n_layers * gnngls::ffn_packed_bytes(), bc, n, part, part_ms, st, lr0));
             } else if (h8) {
               ProfScope ps(GNNGLS_PROF_GAT_ROWS, st);
-              GNNGLS_TRY(gnngls::launch_gat_rows(ft, attn_l, attn_r, bc, n, part, part_ms, st));
+              GNNGLS_TRY(gnngls::launch_gat_rows(ft, p.attn_l, p.attn_r, bc, n, part, part_ms, st));
             } else {
               ProfScope ps(GNNGLS_PROF_GAT_ROWS, st);
-              GNNGLS_TRY(gnngls::launch_gat_heads_rows(ft, attn_l, attn_r, bc, n, n_heads, part, part_ms, hms, st));
+              GNNGLS_TRY(gnngls::launch_gat_heads_rows(ft, p.attn_l, p.attn_r, bc, n, n_heads, part, part_ms, hms, st));
               if (n_heads == 16) GNNGLS_TRY(gnngls::launch_gat_heads_merge16(part, hms, part_ms, M, st)); }
             // gat_combine + FFN1 + FFN2 (+ the next layer's fc) in one launch; the hidden layer and x = BN1(h + GAT) never touch HBM
             { ProfScope ps(GNNGLS_PROF_FFN_FUSED, st);
               // (the last layer's launch also applies the decision layer, models.py:69: its output is never stored)
               const bool last = prep && l + 1 == n_layers;
               const bool lr = l == 0 && lr0;
-              GNNGLS_TRY(gnngls::launch_ffn_fused(part, part_ms, lr ? feat + b0 * N : h, bn1_s, bn1_b, w1, b1, w2, b2, bn2_s, bn2_b, h2, M,
+              GNNGLS_TRY(gnngls::launch_ffn_fused(part, part_ms, lr ? feat + b0 * N : h, p.bn1_g, p.bn1_b, p.w1, p.b1, p.w2, p.b2, p.bn2_g, p.bn2_b, h2, M,
                                                   prep ? prep + (size_t)l * gnngls::ffn_packed_bytes() : nullptr, prep && l + 1 < n_layers, ft, st,
                                                   last ? dec_w : nullptr, last ? dec_b : nullptr, last ? y_out + b0 * N : nullptr,
                                                   lr ? img0 : nullptr, lr ? emb_w : nullptr, lr ? emb_b : nullptr)); }
@@ -746,35 +636,43 @@ int forward_prepared_impl(const float *feat, const float *weights, const void *p
           ProfScope ps(GNNGLS_PROF_DECISION, st);
           GNNGLS_TRY(gnngls::launch_decision(h, dec_w, dec_b, y_out + b0 * N, M, st)); }               // models.py:69
     }
-#undef GNNGLS_TRY
     return GNNGLS_OK;
+}
+
+// The one-call form: splits the weights into stream-ordered scratch of its own on every call (gnngls_regret_prepare +
+// gnngls_regret_forward_prepared keep the image across calls: 2 launches per layer and the allocation saved per forward).
+int forward_one_call(const float *feat, const float *weights, int B, int n, int in_dim, int n_layers, int n_heads,
+                     float *y_out, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (B == 0) return GNNGLS_OK;
+    if (!feat || !weights || !y_out || !workspace || B < 0 || n < 3 || in_dim < 1 || n_layers < 0)
+        return fail(GNNGLS_ERR_ARG, "regret_forward: bad argument");
+    if (n_heads != 8 && n > gnngls::heads_max_nodes())        // (before the scratch image is made)
+        return forward_prepared_impl(feat, weights, nullptr, 0, B, n, in_dim, n_layers, n_heads, y_out, workspace, workspace_bytes, stream);
+    StreamScratch ffn_ws((hipStream_t)stream);
+    static const bool ffn_fp32 = getenv("GNNGLS_FFN_FP32") && atoi(getenv("GNNGLS_FFN_FP32")) != 0;
+    const int64_t pb = gnngls_regret_prepared_bytes(n_layers);
+    if (n_layers > 0 && !ffn_fp32) {
+        hipError_t e = ffn_ws.alloc((size_t)pb);
+        if (e != hipSuccess) return hip_fail(e, "regret_forward: scratch alloc");
+        const int rc = gnngls_regret_prepare(weights, in_dim, n_layers, ffn_ws.p, pb, stream);
+        if (rc != GNNGLS_OK) return rc;
+    }
+    return forward_prepared_impl(feat, weights, ffn_ws.p, pb, B, n, in_dim, n_layers, n_heads, y_out, workspace, workspace_bytes, stream);
 }
 }  // namespace
 
 extern "C" {
 
-// The one-call form: splits the weights into stream-ordered scratch of its own on every call (gnngls_regret_prepare +
-// gnngls_regret_forward_prepared keep the image across calls: 2 launches per layer and the allocation saved per forward).
+int gnngls_regret_forward_prepared(const float *feat, const float *weights, const void *prepared, int64_t prepared_bytes,
+                                   int B, int n, int in_dim, int n_layers,
+                                   float *y_out, void *workspace, int64_t workspace_bytes, void *stream) {
+    return forward_prepared_impl(feat, weights, prepared, prepared_bytes, B, n, in_dim, n_layers, 8, y_out, workspace, workspace_bytes,
+                                 stream);
+}
+
 int gnngls_regret_forward(const float *feat, const float *weights, int B, int n, int in_dim, int n_layers,
                           float *y_out, void *workspace, int64_t workspace_bytes, void *stream) {
-    if (B == 0) return GNNGLS_OK;
-    if (!feat || !weights || !y_out || !workspace || B < 0 || n < 3 || in_dim < 1 || n_layers < 0)
-        return fail(GNNGLS_ERR_ARG, "regret_forward: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    struct StreamScratch {
-        void *p = nullptr; hipStream_t st;
-        ~StreamScratch() { if (p) (void)hipFreeAsync(p, st); }
-    } ffn_ws;
-    ffn_ws.st = st;
-    static const bool ffn_fp32 = getenv("GNNGLS_FFN_FP32") && atoi(getenv("GNNGLS_FFN_FP32")) != 0;
-    const int64_t pb = gnngls_regret_prepared_bytes(n_layers);
-    if (n_layers > 0 && !ffn_fp32) {
-        hipError_t e = hipMallocAsync(&ffn_ws.p, (size_t)pb, st);
-        if (e != hipSuccess) { ffn_ws.p = nullptr; return hip_fail(e, "regret_forward: scratch alloc"); }
-        const int rc = gnngls_regret_prepare(weights, in_dim, n_layers, ffn_ws.p, pb, stream);
-        if (rc != GNNGLS_OK) return rc;
-    }
-    return gnngls_regret_forward_prepared(feat, weights, ffn_ws.p, pb, B, n, in_dim, n_layers, y_out, workspace, workspace_bytes, stream);
+    return forward_one_call(feat, weights, B, n, in_dim, n_layers, 8, y_out, workspace, workspace_bytes, stream);
 }
 
 // ---- head counts other than 8 (embed_dim 128): the same forward with the attention of heads_kernels.hip ----------------------
@@ -782,8 +680,7 @@ int gnngls_model_heads_supported(int n_heads) { return gnngls::heads_supported(n
 
 int64_t gnngls_regret_forward_workspace_bytes_heads(int B, int n, int n_heads) {
     if (!gnngls::heads_supported(n_heads)) return 0;
-    if (n_heads == 8) return gnngls_regret_forward_workspace_bytes(B, n);
-    if (B < 1 || n < 2 || n > 65535) return 0;
+    if (B < 1 || n < 2 || n > 65535) return 0;          // 65535 nodes x 2^31 instances still fits an int64
     const long N = (long)n * (n - 1) / 2;
     return (int64_t)B * N * bytes_per_node(n_heads) + 256;
 }
@@ -806,27 +703,7 @@ int gnngls_regret_forward_prepared_heads(const float *feat, const float *weights
 int gnngls_regret_forward_heads(const float *feat, const float *weights, int B, int n, int in_dim, int n_layers, int n_heads,
                                 float *y_out, void *workspace, int64_t workspace_bytes, void *stream) {
     if (!gnngls::heads_supported(n_heads)) return heads_fail("regret_forward", n_heads);
-    if (n_heads == 8) return gnngls_regret_forward(feat, weights, B, n, in_dim, n_layers, y_out, workspace, workspace_bytes, stream);
-    if (B == 0) return GNNGLS_OK;
-    if (!feat || !weights || !y_out || !workspace || B < 0 || n < 3 || in_dim < 1 || n_layers < 0)
-        return fail(GNNGLS_ERR_ARG, "regret_forward: bad argument");
-    if (n > gnngls::heads_max_nodes())        // (before the scratch image is made)
-        return forward_prepared_impl(feat, weights, nullptr, 0, B, n, in_dim, n_layers, n_heads, y_out, workspace, workspace_bytes, stream);
-    hipStream_t st = (hipStream_t)stream;
-    struct StreamScratch {
-        void *p = nullptr; hipStream_t st;
-        ~StreamScratch() { if (p) (void)hipFreeAsync(p, st); }
-    } ffn_ws;
-    ffn_ws.st = st;
-    static const bool ffn_fp32 = getenv("GNNGLS_FFN_FP32") && atoi(getenv("GNNGLS_FFN_FP32")) != 0;
-    const int64_t pb = gnngls_regret_prepared_bytes(n_layers);
-    if (n_layers > 0 && !ffn_fp32) {
-        hipError_t e = hipMallocAsync(&ffn_ws.p, (size_t)pb, st);
-        if (e != hipSuccess) { ffn_ws.p = nullptr; return hip_fail(e, "regret_forward: scratch alloc"); }
-        const int rc = gnngls_regret_prepare(weights, in_dim, n_layers, ffn_ws.p, pb, stream);
-        if (rc != GNNGLS_OK) return rc;
-    }
-    return forward_prepared_impl(feat, weights, ffn_ws.p, pb, B, n, in_dim, n_layers, n_heads, y_out, workspace, workspace_bytes, stream);
+    return forward_one_call(feat, weights, B, n, in_dim, n_layers, n_heads, y_out, workspace, workspace_bytes, stream);
 }
 
 int gnngls_pack_features(const double *D, int B, int n, double scale, double min_, float *feat, void *stream) {
@@ -905,17 +782,6 @@ TrainWs train_layout(uintptr_t base, long M, int L, int stat_w = 16) {
     return w;
 }
 
-struct LayerParams {
-    const float *fc_w, *attn_l, *attn_r, *bn1_g, *bn1_b, *w1, *b1, *w2, *b2, *bn2_g, *bn2_b;
-};
-
-template <typename T>
-void layer_pointers(T *w, T *&fc_w, T *&attn_l, T *&attn_r, T *&bn1_g, T *&bn1_b, T *&w1, T *&b1, T *&w2, T *&b2, T *&bn2_g,
-                    T *&bn2_b) {
-    fc_w = w; attn_l = fc_w + 128L * 128; attn_r = attn_l + 128; bn1_g = attn_r + 128; bn1_b = bn1_g + 128;
-    w1 = bn1_b + 128; b1 = w1 + 512L * 128; w2 = b1 + 512; b2 = w2 + 128L * 512; bn2_g = b2 + 128; bn2_b = bn2_g + 128;
-}
-
 int train_check(const char *what, const void *feat, const void *params, const void *io, const void *workspace, int B, int n,
                 int in_dim, int n_layers, int64_t workspace_bytes, int n_heads = 8) {
     if (!gnngls::heads_supported(n_heads)) return heads_fail(what, n_heads);
@@ -942,11 +808,7 @@ int train_check(const char *what, const void *feat, const void *params, const vo
 
 extern "C" {
 
-int64_t gnngls_regret_train_workspace_bytes(int B, int n, int n_layers) {
-    if (B < 1 || n < 2 || n > 65535 || n_layers < 0 || n_layers > 4096) return 0;
-    const long M = (long)B * ((long)n * (n - 1) / 2);
-    return (int64_t)train_layout(0, M, n_layers).bytes + 256;
-}
+int64_t gnngls_regret_train_workspace_bytes(int B, int n, int n_layers) { return gnngls_regret_train_workspace_bytes_heads(B, n, n_layers, 8); }
 
 int64_t gnngls_regret_train_workspace_bytes_heads(int B, int n, int n_layers, int n_heads) {
     if (!gnngls::heads_supported(n_heads)) return 0;
@@ -954,8 +816,6 @@ int64_t gnngls_regret_train_workspace_bytes_heads(int B, int n, int n_layers, in
     const long M = (long)B * ((long)n * (n - 1) / 2);
     return (int64_t)train_layout(0, M, n_layers, n_heads == 16 ? 32 : 16).bytes + 256;
 }
-
-#define GNNGLS_TRY(x) do { e = (x); if (e != hipSuccess) return hip_fail(e, #x); } while (0)
 
 int gnngls_regret_train_forward(const float *feat, const float *params, int B, int n, int in_dim, int n_layers, float bn_eps,
                                 float *y_out, float *bn_batch_stats, void *workspace, int64_t workspace_bytes, void *stream) {
@@ -986,38 +846,37 @@ int gnngls_regret_train_forward_heads(const float *feat, const float *params, in
     { ProfScope ps(GNNGLS_PROF_EMBED, st);
       GNNGLS_TRY(gnngls::launch_embed(feat, emb_w, emb_b, w.H, M, in_dim, st)); }                       // models.py:66
     for (int l = 0; l < n_layers; ++l) {                                                                // models.py:67-68
-        const float *fc_w, *attn_l, *attn_r, *bn1_g, *bn1_b, *w1, *b1, *w2, *b2, *bn2_g, *bn2_b;
-        layer_pointers(layers + (long)l * kLayerFloats, fc_w, attn_l, attn_r, bn1_g, bn1_b, w1, b1, w2, b2, bn2_g, bn2_b);
+        const LayerParams<const float> p = layer_params(layers + (long)l * kLayerFloats);
         const float *h = w.H + row * l;
         float *ft = w.FT + row * l, *g = w.G + row * l, *h1 = w.H1 + row * l, *h3 = w.H3 + row * l;
         float *att = w.ATT + (size_t)M * stat_w * l, *bn = w.BN + (size_t)l * 8 * 128;
         float *stats = bn_batch_stats + (size_t)l * 4 * 128;
         int nb = 0;
         { ProfScope ps(GNNGLS_PROF_GEMM_FC, st);
-          GNNGLS_TRY(gnngls::launch_gemm(gnngls::GEMM_EPI_STORE, h, fc_w, ft, M, 128, 128, nullptr, nullptr, nullptr, nullptr, st)); }
+          GNNGLS_TRY(gnngls::launch_gemm(gnngls::GEMM_EPI_STORE, h, p.fc_w, ft, M, 128, 128, nullptr, nullptr, nullptr, nullptr, st)); }
         if (n_heads == 8) {
           { ProfScope ps(GNNGLS_PROF_GAT_ROWS, st);
-            GNNGLS_TRY(gnngls::launch_gat_rows(ft, attn_l, attn_r, B, n, w.PART, w.PMS, st)); }
+            GNNGLS_TRY(gnngls::launch_gat_rows(ft, p.attn_l, p.attn_r, B, n, w.PART, w.PMS, st)); }
           { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
             GNNGLS_TRY(gnngls::launch_gat_combine_train(w.PART, w.PMS, h, M, g, h1, att, st)); }        // models.py:12-15
         } else {
           // (H <= 4: slot statistics, gat_combine_train_kernel as for 8 heads; H = 16: per-head statistics and their own merge)
           { ProfScope ps(GNNGLS_PROF_GAT_ROWS, st);
-            GNNGLS_TRY(gnngls::launch_gat_heads_rows(ft, attn_l, attn_r, B, n, n_heads, w.PART, w.PMS, w.PMS, st)); }
+            GNNGLS_TRY(gnngls::launch_gat_heads_rows(ft, p.attn_l, p.attn_r, B, n, n_heads, w.PART, w.PMS, w.PMS, st)); }
           { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
             if (n_heads == 16) GNNGLS_TRY(gnngls::launch_gat_heads_merge16_train(w.PART, w.PMS, h, M, g, h1, att, st));
             else GNNGLS_TRY(gnngls::launch_gat_combine_train(w.PART, w.PMS, h, M, g, h1, att, st)); }
         }
         { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);                                                   // models.py:27 (train mode)
           GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_SUM_SQ, h1, nullptr, nullptr, M, 128, 0, w.CSP, &nb, st));
-          GNNGLS_TRY(gnngls::launch_bn_stats_finalize(w.CSP, nb, M, bn1_g, bn1_b, bn_eps, bn + 2 * 128, bn + 3 * 128, bn,
+          GNNGLS_TRY(gnngls::launch_bn_stats_finalize(w.CSP, nb, M, p.bn1_g, p.bn1_b, bn_eps, bn + 2 * 128, bn + 3 * 128, bn,
                                                       bn + 128, stats, stats + 128, st)); }
         { ProfScope ps(GNNGLS_PROF_FFN_FUSED, st);                                                      // models.py:28-33
-          GNNGLS_TRY(gnngls::launch_ffn_fused_train(h1, bn + 2 * 128, bn + 3 * 128, w1, b1, w2, b2, ones, zeros, h3,
+          GNNGLS_TRY(gnngls::launch_ffn_fused_train(h1, bn + 2 * 128, bn + 3 * 128, p.w1, p.b1, p.w2, p.b2, ones, zeros, h3,
                                                     w.HID + 4 * row * l, M, st)); }
         { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);                                                   // models.py:35 (train mode)
           GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_SUM_SQ, h3, nullptr, nullptr, M, 128, 0, w.CSP, &nb, st));
-          GNNGLS_TRY(gnngls::launch_bn_stats_finalize(w.CSP, nb, M, bn2_g, bn2_b, bn_eps, bn + 6 * 128, bn + 7 * 128,
+          GNNGLS_TRY(gnngls::launch_bn_stats_finalize(w.CSP, nb, M, p.bn2_g, p.bn2_b, bn_eps, bn + 6 * 128, bn + 7 * 128,
                                                       bn + 4 * 128, bn + 5 * 128, stats + 256, stats + 384, st)); }
         { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
           GNNGLS_TRY(gnngls::launch_affine_cols(h3, bn + 6 * 128, bn + 7 * 128, w.H + row * (l + 1), M, st)); }
@@ -1058,60 +917,57 @@ int gnngls_regret_train_backward_heads(const float *feat, const float *params, c
     { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
       GNNGLS_TRY(gnngls::launch_outer_rows(dy, dec_w, w.DA, M, st)); }
     for (int l = n_layers - 1; l >= 0; --l) {
-        const float *fc_w, *attn_l, *attn_r, *bn1_g, *bn1_b, *w1, *b1, *w2, *b2, *bn2_g, *bn2_b;
-        layer_pointers(layers + (long)l * kLayerFloats, fc_w, attn_l, attn_r, bn1_g, bn1_b, w1, b1, w2, b2, bn2_g, bn2_b);
-        float *d_fc_w, *d_attn_l, *d_attn_r, *d_bn1_g, *d_bn1_b, *d_w1, *d_b1, *d_w2, *d_b2, *d_bn2_g, *d_bn2_b;
-        layer_pointers(g_layers + (long)l * kLayerFloats, d_fc_w, d_attn_l, d_attn_r, d_bn1_g, d_bn1_b, d_w1, d_b1, d_w2,
-                       d_b2, d_bn2_g, d_bn2_b);
+        const LayerParams<const float> p = layer_params(layers + (long)l * kLayerFloats);
+        const LayerParams<float> d = layer_params(g_layers + (long)l * kLayerFloats);
         const float *h = w.H + row * l, *ft = w.FT + row * l, *g = w.G + row * l, *h1 = w.H1 + row * l, *h3 = w.H3 + row * l;
         const float *att = w.ATT + (size_t)M * stat_w * l, *bn = w.BN + (size_t)l * 8 * 128;
         // BatchNorm 2 backward (models.py:35): DA = d(layer output) -> DB = d h3
         { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);
           GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_SUM_PROD, w.DA, h3, nullptr, M, 128, 0, w.CSP, &nb, st));
-          GNNGLS_TRY(gnngls::launch_bn_bwd_finalize(w.CSP, nb, M, bn2_g, bn + 4 * 128, bn + 5 * 128, d_bn2_g, d_bn2_b, w.COEF, st)); }
+          GNNGLS_TRY(gnngls::launch_bn_bwd_finalize(w.CSP, nb, M, p.bn2_g, bn + 4 * 128, bn + 5 * 128, d.bn2_g, d.bn2_b, w.COEF, st)); }
         { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
           // d h3 = BatchNorm-2 backward of DA, and x = BN1(h1) recomputed, in one elementwise pass
           GNNGLS_TRY(gnngls::launch_bn_bwd_apply_and_affine(w.DA, h3, bn + 4 * 128, w.COEF, w.DB, h1, bn + 2 * 128, bn + 3 * 128,
                                                             w.X2, M, st));
-          GNNGLS_TRY(gnngls::launch_transpose_pair(w2, w1, w.WT, w.WT + 512 * 128, st)); }              // W2^T, W1^T
+          GNNGLS_TRY(gnngls::launch_transpose_pair(p.w2, p.w1, w.WT, w.WT + 512 * 128, st)); }              // W2^T, W1^T
         // feed-forward block backward (models.py:28-33): h3 = x + W2 relu(W1 x + b1) + b2
         float *hid = w.HID + 4 * row * l;                    // saved ReLU(W1 x + b1)
         { ProfScope ps(GNNGLS_PROF_TRAIN_GEMM_TN, st);
-          GNNGLS_TRY(gnngls::launch_gemm_tn(w.DB, hid, M, 128, 512, w.TNP, d_w2, d_b2, st)); }   // d W2 and d b2 = colsum(d h3)
+          GNNGLS_TRY(gnngls::launch_gemm_tn(w.DB, hid, M, 128, 512, w.TNP, d.w2, d.b2, st)); }   // d W2 and d b2 = colsum(d h3)
         { ProfScope ps(GNNGLS_PROF_TRAIN_GEMM_BWD, st);      // d x = ((d h3 * W2) . [relu > 0]) * W1 + d h3; hid <- d pre
           GNNGLS_TRY(gnngls::launch_ffn_fused_bwd(w.DB, w.WT, w.WT + 512 * 128, w.COEF + 3 * 128, w.COEF + 4 * 128, w.DA, hid, M, st)); }
         { ProfScope ps(GNNGLS_PROF_TRAIN_GEMM_TN, st);
-          GNNGLS_TRY(gnngls::launch_gemm_tn(hid, w.X2, M, 512, 128, w.TNP, d_w1, d_b1, st)); }   // d W1 and d b1 = colsum(d pre)
+          GNNGLS_TRY(gnngls::launch_gemm_tn(hid, w.X2, M, 512, 128, w.TNP, d.w1, d.b1, st)); }   // d W1 and d b1 = colsum(d pre)
         // BatchNorm 1 backward (models.py:27): DA = d x -> DB = d h1 (= d h through the skip, = d GATConv output)
         { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);
           GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_SUM_PROD, w.DA, h1, nullptr, M, 128, 0, w.CSP, &nb, st));
-          GNNGLS_TRY(gnngls::launch_bn_bwd_finalize(w.CSP, nb, M, bn1_g, bn, bn + 128, d_bn1_g, d_bn1_b, w.COEF, st)); }
+          GNNGLS_TRY(gnngls::launch_bn_bwd_finalize(w.CSP, nb, M, p.bn1_g, bn, bn + 128, d.bn1_g, d.bn1_b, w.COEF, st)); }
         { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
           GNNGLS_TRY(gnngls::launch_bn_bwd_apply(w.DA, h1, bn, w.COEF, w.DB, M, st)); }
         // GATConv backward (models.py:23)
         if (n_heads == 16) {        // per-head d el / d er: combine and attention-vector sums of their own
           { ProfScope ps(GNNGLS_PROF_TRAIN_GAT_BWD, st);
-            GNNGLS_TRY(gnngls::launch_gat_heads_bwd_rows(ft, w.DB, g, att, attn_l, attn_r, B, n, n_heads, w.PART, w.PMS, st)); }
+            GNNGLS_TRY(gnngls::launch_gat_heads_bwd_rows(ft, w.DB, g, att, p.attn_l, p.attn_r, B, n, n_heads, w.PART, w.PMS, st)); }
           { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
-            GNNGLS_TRY(gnngls::launch_gat_heads_bwd_combine16(w.PART, w.PMS, attn_l, attn_r, M, w.DFT, w.DLR, w.DLR + (size_t)M * 16, st)); }
+            GNNGLS_TRY(gnngls::launch_gat_heads_bwd_combine16(w.PART, w.PMS, p.attn_l, p.attn_r, M, w.DFT, w.DLR, w.DLR + (size_t)M * 16, st)); }
           { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);
             nb = gnngls::colsum_blocks(M, 128);
             GNNGLS_TRY(gnngls::launch_colsum_heads16(ft, w.DLR, w.DLR + (size_t)M * 16, M, w.CSP, nb, st));
-            GNNGLS_TRY(gnngls::launch_colsum_store(w.CSP, nb, 128, 1, d_attn_l, d_attn_r, st)); }
+            GNNGLS_TRY(gnngls::launch_colsum_store(w.CSP, nb, 128, 1, d.attn_l, d.attn_r, st)); }
         } else {
           { ProfScope ps(GNNGLS_PROF_TRAIN_GAT_BWD, st);
-            if (n_heads == 8) GNNGLS_TRY(gnngls::launch_gat_bwd_rows(ft, w.DB, g, att, attn_l, attn_r, B, n, w.PART, w.PMS, st));
-            else GNNGLS_TRY(gnngls::launch_gat_heads_bwd_rows(ft, w.DB, g, att, attn_l, attn_r, B, n, n_heads, w.PART, w.PMS, st)); }
+            if (n_heads == 8) GNNGLS_TRY(gnngls::launch_gat_bwd_rows(ft, w.DB, g, att, p.attn_l, p.attn_r, B, n, w.PART, w.PMS, st));
+            else GNNGLS_TRY(gnngls::launch_gat_heads_bwd_rows(ft, w.DB, g, att, p.attn_l, p.attn_r, B, n, n_heads, w.PART, w.PMS, st)); }
           { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
-            GNNGLS_TRY(gnngls::launch_gat_bwd_combine(w.PART, w.PMS, attn_l, attn_r, M, w.DFT, w.DLR, w.DLR + (size_t)M * 8, st)); }
+            GNNGLS_TRY(gnngls::launch_gat_bwd_combine(w.PART, w.PMS, p.attn_l, p.attn_r, M, w.DFT, w.DLR, w.DLR + (size_t)M * 8, st)); }
           { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);
             GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_HEADSCALE, ft, w.DLR, w.DLR + (size_t)M * 8, M, 128, 0, w.CSP, &nb, st));
-            GNNGLS_TRY(gnngls::launch_colsum_store(w.CSP, nb, 128, 1, d_attn_l, d_attn_r, st)); }
+            GNNGLS_TRY(gnngls::launch_colsum_store(w.CSP, nb, 128, 1, d.attn_l, d.attn_r, st)); }
         }
         { ProfScope ps(GNNGLS_PROF_TRAIN_GEMM_TN, st);
-          GNNGLS_TRY(gnngls::launch_gemm_tn(w.DFT, h, M, 128, 128, w.TNP, d_fc_w, nullptr, st)); }
+          GNNGLS_TRY(gnngls::launch_gemm_tn(w.DFT, h, M, 128, 128, w.TNP, d.fc_w, nullptr, st)); }
         { ProfScope ps(GNNGLS_PROF_TRAIN_GEMM_BWD, st);      // d h = d ft * Wfc + d h1 (skip, models.py:15)
-          GNNGLS_TRY(gnngls::launch_gemm_wkn(gnngls::GEMM_EPI_ADD, w.DFT, fc_w, w.DA, M, 128, 128, w.DB, st)); }
+          GNNGLS_TRY(gnngls::launch_gemm_wkn(gnngls::GEMM_EPI_ADD, w.DFT, p.fc_w, w.DA, M, 128, 128, w.DB, st)); }
     }
     // embedding (models.py:66): h0 = x We^T + be
     { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);
@@ -1159,7 +1015,7 @@ int gnngls_debug_set_gls_threads(int threads) {
     // picks them itself where a workgroup owns a CU); the 64- and 80-VGPR builds are bounded at 512 threads
     if (threads != 0 && threads != 64 && threads != 128 && threads != 256 && threads != 512)
         return fail(GNNGLS_ERR_ARG, "gls threads override must be 0 (default policy), 64, 128, 256 or 512");
-    gnngls::gls_set_block_threads_override(threads);
+    g_threads_override.store(threads, std::memory_order_relaxed);
     return GNNGLS_OK;
 }
 

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "constructors_kernels.h"
+#include "gls_policy.h"
 
 #pragma clang fp contract(off)
 

@@ -16,14 +16,8 @@
 #define GLS_NODE_LANES 0             // relocate descent scan: lanes own tour positions (0) or node ids (1: 21 % fewer LDS
                                      // bank-conflict cycles, 1 % FEWER iterations -- profiles/r03_experiments/README.md)
 #endif
-#ifndef GLS_WPS2
-#define GLS_WPS2 1                   // 256-VGPR build of the one-slot kernel for batches of <= 2 single-wavefront workgroups per SIMD (TSP20 x 1000:
-                                     // groups of 4 steps in the half-wave scans without scratch, +3 %; profiles/r04_experiments)
-#endif
-#ifndef GLS_PRUNE_MAX_WPS
-#define GLS_PRUNE_MAX_WPS 6          // register budgets (waves per SIMD) whose instantiations carry the pruned descent scans: not the
-                                     // 64-VGPR builds (batches of small instances: scratch 148 -> 100 B, +0.8 %; profiles/r04_experiments)
-#endif
+// (GLS_WPS2, GLS_PRUNE_MAX_WPS, GLS_HALF_SCANS, GLS_EDGE_PERTURB and the constants the launch plan shares with the kernels --
+// kWave, kGuidePassesMax, the half-scan and pruning thresholds -- live in gls_policy.h, included by the unit before this file)
 #ifndef GLS_TEAM_NODE_SUBST
 #define GLS_TEAM_NODE_SUBST 1        // team form: known-count substitution decided by node compares (uniform part on the scalar unit)
 #endif
@@ -39,9 +33,7 @@
 #ifndef GLS_LEAN_UNROLL_RELOCATE
 #define GLS_LEAN_UNROLL_RELOCATE 6   // the relocate scan: with one exec-masked test per group (group_may_improve) six steps per group win
 #endif
-constexpr int kWave = 64;
 constexpr int kNoKey = INT_MAX;
-constexpr int kGuidePassesMax = 4;   // register-cached guide values cover n <= 256
 
 // Diagnostic build only (-DGLS_STAMPS): per-phase shader-cycle totals of the search kernel, written to
 // a side buffer that nothing else reads.  The shipped library is built without it.
@@ -96,7 +88,7 @@ struct TriStore {
     using tour_t = int32_t;
     static constexpr bool kSymmetric = true;
     static constexpr bool kPenInLds = true;
-    static constexpr int kWavesPerSimd = 6;      // 3 workgroups of 8 waves per CU
+    static constexpr int kWavesPerSimd = kTriWavesPerSimd;      // 3 workgroups of 8 waves per CU
     static constexpr int kScanUnroll = 1;        // 80-VGPR budget: no room for batched evaluations
     __device__ __forceinline__ static int idx(int a, int b) {
         int hi = a > b ? a : b, lo = a > b ? b : a;
@@ -149,7 +141,7 @@ struct TriDGlobalP {
     using tour_t = uint8_t;                       // n <= 255
     static constexpr bool kSymmetric = true;
     static constexpr bool kPenInLds = false;
-    static constexpr int kWavesPerSimd = 4;      // default register budget (128 VGPRs); the launcher also builds an 8-wave variant
+    static constexpr int kWavesPerSimd = kCompactWavesPerSimd;      // default register budget (128 VGPRs); the launcher also builds an 8-wave variant
     static constexpr int kScanUnroll = 1;        // measured: 2-deep batching costs more in spills than it hides (8.6k vs 10.0k)
     __device__ __forceinline__ static int idx(int a, int b) {
         int hi = a > b ? a : b, lo = a > b ? b : a;
@@ -240,7 +232,7 @@ struct GlobalStore {
     using pen_t = int32_t;
     using tour_t = int32_t;
     static constexpr bool kPenInLds = false;
-    static constexpr int kWavesPerSimd = 4;
+    static constexpr int kWavesPerSimd = kGlobalWavesPerSimd;
     static constexpr int kScanUnroll = 2;
     __device__ __forceinline__ bool pen_inc(int a, int b) const {
         p[(size_t)a * n + b] += 1;

@@ -759,13 +759,9 @@ __device__ __forceinline__ void scan_two_opt_a2a_lean(const S &s, const TT *t, c
 // owns row 1 + l in both halves and half h walks half of the other index (relocate: target edges k, 2-opt: j), so a scan
 // takes half the steps.  The node of a step is no longer wave-uniform: two v_readlane and a select per step, and its row
 // address is vector arithmetic.  Same deltas (same operands, same order), same keys; within a lane the keys still ascend.
-#ifndef GLS_HALF_SCANS
-#define GLS_HALF_SCANS 1
-#endif
 #ifndef GLS_HALF_UNROLL
 #define GLS_HALF_UNROLL 3             // steps per group of the half-wave scans (4: 2 % faster at TSP20, 8 B of scratch)
 #endif
-constexpr int kHalfScanMinNodes = 8, kHalfScanMaxNodes = 33;
 
 template <int HUN, class S, class TT>
 __device__ __forceinline__ void scan_relocate_a2a_lean_half(const S &s, const TT *t, const double *Ef, int n, int lane,
@@ -918,7 +914,6 @@ struct NlWords {
         return it == 0 ? w0 : it == 1 ? w1 : it == 2 ? w2 : w3;
     }
 };
-constexpr int kPruneMinNodes = 80;       // 2-opt scan pruned from here up (same-box A/B at n = 66 .. 127), relocate from n = 128
 
 template <bool CNT, class S, class TT>
 __device__ __forceinline__ void scan_two_opt_a2a_pruned(const S &s, const TT *t, const TT *pos, const double *Ef,

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gls_plan.h"
+
 #define GNNGLS_STATUS_WATCHDOG_DEV 1
 #define GNNGLS_STATUS_PENALTY_OVERFLOW_DEV 2
 #define GNNGLS_STATUS_ASYMMETRIC_DEV 3
@@ -46,30 +48,17 @@ struct GlsArgs {
     const int32_t *asym;       // [B] 1 = the instance's matrix is not bitwise symmetric (symmetric stores: not searched, status 3); or NULL
 };
 
-enum { GLS_STORE_GLOBAL = 0, GLS_STORE_TRI = 1, GLS_STORE_COMPACT = 2 };
-size_t gls_lds_bytes(int n, int store, int penalty_bits, bool team = false);
-int gls_block_threads(int n, int store, int penalty_bits = 32, bool half_scans = true);
-void gls_set_block_threads_override(int threads);   // 0 = default policy (experiments only)
-// resident wavefronts per SIMD (= register budget) of the kernel instantiation for this configuration: 4 or 8 for the
-// compact store, fixed for the others
-int gls_waves_per_simd(int store, int n, int batch, int num_cus, int threads, size_t lds);
-// team: perturbation phase on all wavefronts of the workgroup (for workgroups that own their CU); only where
-// gls_team_supported() says so
-bool gls_team_supported(int store, int penalty_bits, int wps, int n, int threads);
-bool gls_edge_form(int store, int penalty_bits, int wps, bool team, bool first_improvement);
-bool gls_wps2_supported(int store, int penalty_bits, int n, int threads, bool first_improvement);
-hipError_t launch_gls(const GlsArgs &A, int store, int penalty_bits, int threads, int wps, bool team, bool first_improvement,
-                      hipStream_t stream);
-hipError_t gls_kernel_resources(const GlsArgs &A, int store, int penalty_bits, int threads, int wps, bool team, bool first_improvement,
-                                int *vgprs, int *scratch_bytes);
+// the instantiation of the persistent kernel a plan runs on (nullptr: the plan names none), its launch, and its registers and
+// scratch (hipFuncGetAttributes: needs the device)
+const void *gls_kernel_fn(const GlsPlan &p);
+hipError_t launch_gls(const GlsArgs &A, const GlsPlan &p, hipStream_t stream);
+hipError_t gls_kernel_resources(const GlsPlan &p, int *vgprs, int *scratch_bytes);
 constexpr int kNeighborListLen = 32;
-bool gls_prune_supported(int store, int n, bool first_improvement, int wps);
-bool gls_count_supported(int store, int wps, int n, bool first_improvement, bool trace);
 hipError_t launch_symmetry_check(const double *D, int B, int n, int32_t *asym, hipStream_t stream);
 hipError_t launch_neighbor_lists(const double *D, int B, int n, uint8_t *nl_id, int32_t *prune_ok, hipStream_t stream);
 hipError_t launch_delta_all(const int32_t *tour, const double *D, int B, int n, int op, double *out, hipStream_t stream);
 hipError_t launch_best_move(const int32_t *tour, const double *D, int B, int n, int op, const int32_t *pos_i,
-                            bool first_improvement, double *delta_out, int32_t *move_out, int32_t *new_tour,
+                            bool first_improvement, int threads, double *delta_out, int32_t *move_out, int32_t *new_tour,
                             hipStream_t stream);
 hipError_t launch_tour_cost(const int32_t *tour, const double *D, int B, int n, double *out, hipStream_t stream);
 hipError_t launch_nearest_neighbor(const double *W, int B, int n, int depot, int32_t *tour_out, hipStream_t stream);

@@ -37,13 +37,14 @@
 // One translation unit in four files (round 5; the code generation of the ~70 kernel instantiations depends on all of it, so it
 // stays one unit): gls_common.h (switches, storage policies, move evaluation, selection, reductions), gls_descent_scans.h (the
 // all-to-all scans of the descent), gls_perturbation.h (one-to-all scans and the three forms of the perturbation phase), and this
-// file (local_search, the persistent kernel, unit kernels, launch policy).
+// file (local_search, the persistent kernel, unit kernels, the launchers).  The launch policy is not here: gls_plan.cpp (plain host
+// C++) makes a GlsPlan from the request, gls_kernel_fn below maps the plan to its instantiation, and gls_policy.h holds the
+// switches, thresholds and compile-time rules (edge_form_of, can_prune_of) that the kernels and the plan share.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
 #include <stdint.h>
 
-#include <atomic>
 #include <type_traits>
 
 #include "gls_kernels.h"
@@ -105,7 +106,7 @@ __device__ __forceinline__ void local_search_dev(const S &s, TT *&t, TT *&t2, do
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     // pruned descent scans (given neighbour lists): the 2-opt scan from n = 80 up, the relocate scan from n = 128 up (the
     // 4-slot instantiations) -- where each was measured faster (profiles/r03_experiments/README.md)
-    constexpr bool kCanPrune = !FI && S::kSymmetric && WPS <= GLS_PRUNE_MAX_WPS;
+    constexpr bool kCanPrune = can_prune_of(FI, S::kSymmetric, WPS);
     // steps per group of the half-wave scans: 4 on the 256-VGPR build (no scratch there), else GLS_HALF_UNROLL
     constexpr int kHalfUnroll = WPS <= 2 ? 4 : GLS_HALF_UNROLL;
     constexpr bool kPruneRelocate = kCanPrune && GP == 4;
@@ -327,7 +328,7 @@ __global__ __launch_bounds__(WPS <= 2 ? 256 : WPS <= 4 ? 1024 : 512, WPS) void g
     const int n = A.n;
     const int tid = threadIdx.x, nthr = blockDim.x;
     // the edge form of the serial perturbation phase: best improvement, 32-bit counters, the 128-VGPR (and wider) builds
-    constexpr bool kEdgeForm = GLS_EDGE_PERTURB && S::kSymmetric && !FI && !TEAM && sizeof(typename S::pen_t) == 4 && WPS <= 4;
+    constexpr bool kEdgeForm = edge_form_of(S::kSymmetric, sizeof(typename S::pen_t), FI, TEAM, WPS);
     // wave-uniform by construction; as a SCALAR it keeps `if (wave == 0)` -- the serial perturbation phase -- a scalar branch and
     // what the phase modifies (tour pointers, cost, counters) out of the exec-masked phis of a divergent one.  Measured
     // (profiles/r05_experiments/): +1 % for the team form, needed by the edge form, -4 % for the scan-by-scan form (whose code
@@ -437,7 +438,7 @@ __global__ __launch_bounds__(WPS <= 2 ? 256 : WPS <= 4 ? 1024 : 512, WPS) void g
     if (!FI && nthr > kWave) { block_reduce_lds_init(ctl, tid); __syncthreads(); }
     STAMP_BEGIN();
     PruneCtx pc{{0u, 0u, 0u, 0u}, false};
-    if constexpr (!FI && S::kSymmetric && WPS <= GLS_PRUNE_MAX_WPS) {
+    if constexpr (can_prune_of(FI, S::kSymmetric, WPS)) {
         // (a workgroup too small to hold its rows' list words in kNlPasses registers per lane runs the full scans)
         if (A.nl_id && A.prune_ok[b] && 8 * (n - 1) <= kNlPasses * nthr) {
             const uint8_t *nl = A.nl_id + (size_t)b * n * kNL;
@@ -803,201 +804,78 @@ __global__ void nearest_neighbor_kernel(const double *W, int n, int depot, int32
 // ---------------------------------------------------------------------------------------------
 // Host-side launchers
 // ---------------------------------------------------------------------------------------------
-size_t gls_lds_bytes(int n, int store, int penalty_bits, bool team) {
-    auto r16 = [](size_t x) { return (x + 15) & ~size_t(15); };
-    const size_t tour_elem = store == GLS_STORE_COMPACT ? 1 : 4;
-    size_t off = r16(sizeof(Ctl)) + r16((size_t)(n + 2) * 8) + 3 * r16((size_t)(n + 1) * tour_elem);
-    if (team) off += r16(sizeof(TeamCtl));
-    if (store == GLS_STORE_GLOBAL) off += r16((size_t)(n + 2) * 8);
-    size_t ntri = (size_t)n * (n - 1) / 2;
-    if (store != GLS_STORE_GLOBAL) off += r16(ntri * 8);
-    if (store == GLS_STORE_TRI) off += r16(ntri * (size_t)(penalty_bits / 8));
-    return off;
+static_assert(sizeof(Ctl) == kCtlBytes && sizeof(TeamCtl) == kTeamCtlBytes, "gls_policy.h and the LDS control blocks disagree");
+
+// Plan -> instantiation: one case per gls_kernel<S, FI, GP, TR, WPS, TEAM, CNT> that exists, keyed by the plan's fields
+// (REC: what the run records per move -- nothing, the trace, the executed evaluations)
+enum { kRecNone, kRecTrace, kRecCount };
+constexpr unsigned gls_key(int store, int bits, int wps, bool team, bool fi, int gp, int rec) {
+    return ((((((unsigned)store * 64 + bits) * 16 + wps) * 2 + team) * 2 + fi) * 8 + gp) * 4 + rec;
 }
+#define GLS_CASE(STORE, BITS, S, WPS, TEAM, FI, GP, REC)  \
+    case gls_key(STORE, BITS, WPS, TEAM, FI, GP, REC):    \
+        return reinterpret_cast<const void *>(&gls_kernel<S, FI, GP, REC == kRecTrace, WPS, TEAM, REC == kRecCount>);
+// trace_cap == 0 (no trace buffer): the trace-free instantiation (fewer live registers in the serial phase)
+#define GLS_CASE_TR(STORE, BITS, S, WPS, TEAM, FI, GP) \
+    GLS_CASE(STORE, BITS, S, WPS, TEAM, FI, GP, kRecNone) GLS_CASE(STORE, BITS, S, WPS, TEAM, FI, GP, kRecTrace)
+// a store at a register budget, with or without the team form: first and best improvement, two or four register slots
+#define GLS_FAMILY(STORE, BITS, S, WPS, TEAM)                                                        \
+    GLS_CASE_TR(STORE, BITS, S, WPS, TEAM, false, 2) GLS_CASE_TR(STORE, BITS, S, WPS, TEAM, false, 4) \
+    GLS_CASE_TR(STORE, BITS, S, WPS, TEAM, true, 2) GLS_CASE_TR(STORE, BITS, S, WPS, TEAM, true, 4)
+#define GLS_CASE_COUNT(S, TEAM) /* counting instantiations (gls_plan.cpp: count) */ \
+    GLS_CASE(GLS_STORE_COMPACT, 32, S, 4, TEAM, false, 2, kRecCount) GLS_CASE(GLS_STORE_COMPACT, 32, S, 4, TEAM, false, 4, kRecCount)
 
-static std::atomic<int> g_threads_override{0};      // experiments only (gnngls_debug_set_gls_threads)
-void gls_set_block_threads_override(int threads) { g_threads_override.store(threads, std::memory_order_relaxed); }
-
-int gls_block_threads(int n, int store, int penalty_bits, bool half_scans) {
-    const int forced = g_threads_override.load(std::memory_order_relaxed);
-    if (forced > 0) return forced;
-    if (n <= 24) return 64;
-    // n <= 33 on the stores that have the half-wave descent scans: ONE wavefront using both its 32-lane halves beats two
-    // wavefronts sharing the lean scans (outer iterations in 2 s, x 1000, noise guide: n = 26 24.2k -> 25.7k, n = 30 22.6k ->
-    // 24.1k, n = 33 21.1k -> 22.4k)
-    // (half_scans = false: the caller knows the launch ends up on an instantiation without them -- first improvement, or the
-    // 64- / 80-VGPR builds -- where one wavefront would run the two-wavefront scans alone)
-    if (GLS_HALF_SCANS && half_scans && n <= kHalfScanMaxNodes && penalty_bits == 32 && (store == GLS_STORE_COMPACT || store == GLS_STORE_TRI))
-        return 64;
-    if (n <= 48) return 128;
-    if (n <= 80) return 256;
-    // compact store with the lean descent scans (n <= 127), four workgroups per CU, measured at TSP100 x 1024 (outer
-    // iterations per instance in 2 s, weight / noise guide): 8 waves at 64 VGPRs (108 B of scratch) 11.6k / 7.0k;
-    // 4 waves at 128 VGPRs (no scratch) 12.3k / 7.5k  <- used.  (One workgroup alone on a CU prefers 8 waves, 16.1k vs
-    // 14.8k, but such small batches run on the LDS-penalty store anyway.)
-    if (store == GLS_STORE_COMPACT && n <= 2 * kWave - 1) return 256;
-    // compact store with ONE workgroup per CU (distance triangle > 80 KB, n >= 144; TSP200): the descent is latency-bound
-    // at two waves per SIMD -- 16 waves share the scans (measured TSP200 x 256, noise guide, iterations in 2 s: 8 waves
-    // 4.7k, 16 waves see profiles/)
-    if (store == GLS_STORE_COMPACT && 2 * gls_lds_bytes(n, GLS_STORE_COMPACT, 32) > 160 * 1024) return 1024;
-    return 512;
-}
-
-int gls_waves_per_simd(int store, int n, int batch, int num_cus, int threads, size_t lds) {
-    if (store == GLS_STORE_GLOBAL) return GlobalStore::kWavesPerSimd;
-    if (store == GLS_STORE_TRI) {
-        // LDS-penalty store: the 128-VGPR build (no scratch) while it keeps the batch resident, else the 80-VGPR one
-        const int waves = threads / kWave;
-        const int by_lds = (int)((160 * 1024) / lds);
-        const int per_cu4 = by_lds < 16 / waves ? by_lds : 16 / waves;
-        // ... and only where the smaller register budget actually buys residency (n = 150: one workgroup per CU by LDS
-        // either way -- the 80-VGPR build spills for nothing)
-        const int per_cu6 = by_lds < 24 / waves ? by_lds : 24 / waves;
-        if (batch > 0 && per_cu4 >= 1 && ((long)per_cu4 * num_cus >= batch || per_cu6 <= per_cu4)) return 4;
-        return TriStore<int32_t>::kWavesPerSimd;
+const void *gls_kernel_fn(const GlsPlan &p) {
+#ifdef GLS_DEV_ONLY_HEADLINE
+    // development builds (ISA inspection, fast compiles): only the instantiation the TSP100 x 1024 headline runs on
+    (void)p;
+    return reinterpret_cast<const void *>(&gls_kernel<TriDGlobalP, false, GLS_DEV_ONLY_HEADLINE + 0 == 4 ? 4 : 2, false, 4, false>);   // (-DGLS_DEV_ONLY_HEADLINE=4: TSP200's)
+#else
+    switch (gls_key(p.store, p.penalty_bits, p.wps, p.team, p.first_improvement, p.gp, p.count ? kRecCount : p.trace ? kRecTrace : kRecNone)) {
+    // compact store: the 128-VGPR build, its 64-VGPR build for batches that only fit with 8 waves per SIMD, the team form
+    // (counters in a full matrix: TriDGlobalPF)
+    GLS_FAMILY(GLS_STORE_COMPACT, 32, TriDGlobalP, 4, false) GLS_CASE_COUNT(TriDGlobalP, false)
+    GLS_FAMILY(GLS_STORE_COMPACT, 32, TriDGlobalP, 8, false)
+    GLS_FAMILY(GLS_STORE_COMPACT, 32, TriDGlobalPF, 4, true) GLS_CASE_COUNT(TriDGlobalPF, true)
+    // LDS-penalty store: 32-bit counters on the 128- and 80-VGPR builds and as the team form, 16-bit counters on the 80-VGPR build
+    GLS_FAMILY(GLS_STORE_TRI, 32, TriStore<int32_t>, 4, false)
+    GLS_FAMILY(GLS_STORE_TRI, 32, TriStore<int32_t>, kTriWavesPerSimd, false)
+    GLS_FAMILY(GLS_STORE_TRI, 32, TriStore<int32_t>, 4, true)
+    GLS_FAMILY(GLS_STORE_TRI, 16, TriStore<uint16_t>, kTriWavesPerSimd, false)
+    GLS_FAMILY(GLS_STORE_GLOBAL, 32, GlobalStore, kGlobalWavesPerSimd, false)
+    // the one-slot instantiations (gls_plan.cpp: guide_passes)
+    GLS_CASE_TR(GLS_STORE_COMPACT, 32, TriDGlobalP, 4, false, false, 1)
+    GLS_CASE_TR(GLS_STORE_TRI, 32, TriStore<int32_t>, 4, false, false, 1)
+#if GLS_WPS2
+    // ... and its 256-VGPR build: single-wavefront workgroups, at most two per SIMD
+    GLS_CASE_TR(GLS_STORE_COMPACT, 32, TriDGlobalP, 2, false, false, 1)
+    GLS_CASE_TR(GLS_STORE_TRI, 32, TriStore<int32_t>, 2, false, false, 1)
+#endif
+    default: return nullptr;
     }
-    // compact store: the 128-VGPR build unless the batch only fits with 8 waves per SIMD
-    const int waves = threads / kWave;
-    const int by_lds = (int)((160 * 1024) / lds);
-    const int per_cu4 = by_lds < 16 / waves ? by_lds : 16 / waves;
-    (void)n;
-    return (batch > 0 && (long)per_cu4 * num_cus < batch && 32 / waves > per_cu4 && by_lds > per_cu4) ? 8 : 4;
+#endif
 }
 
-// resource query (gls_kernel_resources): with the slot set, the launch chain stops at the selected instantiation and hands back
-// its function instead of launching it
-static thread_local const void **t_query_fn = nullptr;
-
-template <class S, bool FI, int GP, bool TR, int WPS, bool TEAM, bool CNT = false>
-static hipError_t launch_gls_k(const GlsArgs &A, size_t lds, int threads, hipStream_t stream) {
-    auto kern = gls_kernel<S, FI, GP, TR, WPS, TEAM, CNT>;
-    if (t_query_fn) { *t_query_fn = reinterpret_cast<const void *>(kern); return hipSuccess; }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+hipError_t launch_gls(const GlsArgs &A, const GlsPlan &p, hipStream_t stream) {
+    const void *fn = gls_kernel_fn(p);
+    if (!fn) return hipErrorInvalidValue;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
     if (e != hipSuccess) return e;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3(A.B), dim3(threads), lds, stream, A);
+    void *args[] = {const_cast<GlsArgs *>(&A)};
+    (void)hipLaunchKernel(fn, dim3(A.B), dim3(p.threads), args, p.lds, stream);
     return hipGetLastError();
 }
 
-template <class S, bool FI, int GP, int WPS, bool TEAM>
-static hipError_t launch_gls_g(const GlsArgs &A, size_t lds, int threads, hipStream_t stream) {
-    // counting instantiations (executed evaluations of the pruned scans): compact store, best improvement, 128-VGPR build,
-    // no per-move trace -- gls_count_supported() says the same to the host
-    if constexpr (!FI && WPS == 4 && GP >= 2 && std::is_base_of<TriDGlobalP, S>::value) {
-        if (A.evals_exec && A.nl_id && !(A.trace_cap > 0 && A.trace_cost)) return launch_gls_k<S, FI, GP, false, WPS, TEAM, true>(A, lds, threads, stream);
-    }
-    // (a run that prunes AND asks for the executed-evaluation count must have landed on a counting instantiation above: the
-    // others would report executed == reference evaluations, a silently wrong ratio -- gls_count_supported() is the host's copy
-    // of the rule)
-    if (A.evals_exec && A.nl_id) return hipErrorInvalidValue;
-    // trace_cap == 0 (no trace buffer): the trace-free instantiation (fewer live registers in the serial phase)
-    if (A.trace_cap > 0 && A.trace_cost) return launch_gls_k<S, FI, GP, true, WPS, TEAM>(A, lds, threads, stream);
-    return launch_gls_k<S, FI, GP, false, WPS, TEAM>(A, lds, threads, stream);
-}
-
-template <class S, bool FI, int WPS, bool TEAM>
-static hipError_t launch_gls_t(const GlsArgs &A, size_t lds, int threads, hipStream_t stream) {
-    // small instances on single-wavefront workgroups (TSP20): the one-slot instantiation, whose descent scans use both
-    // 32-lane halves of the wavefront (scan_*_a2a_lean_half) -- an instantiation of its own so that the register
-    // allocation of the others (the TSP100 headline runs on GP = 2) does not see that code
-    if constexpr (!FI && !TEAM && WPS == 4 && S::kSymmetric && sizeof(typename S::pen_t) == 4) {
-        if (GLS_HALF_SCANS && A.n >= kHalfScanMinNodes && A.n <= kHalfScanMaxNodes && threads == kWave)
-            return launch_gls_g<S, FI, 1, WPS, TEAM>(A, lds, threads, stream);
-        // the edge form of the serial perturbation phase evaluates every register slot of a lane: n <= 63 (tour positions
-        // 0 .. n in one slot) runs on the one-slot instantiation whatever the workgroup shape (TSP50)
-        if (GLS_EDGE_PERTURB && A.n <= kWave - 1) return launch_gls_g<S, FI, 1, WPS, TEAM>(A, lds, threads, stream);
-    }
-    // register-cached guide/penalty values of the tour edges: 2 passes of 64 lanes cover positions 0..n for n <= 127
-    if (A.n + 1 <= 2 * kWave) return launch_gls_g<S, FI, 2, WPS, TEAM>(A, lds, threads, stream);
-    return launch_gls_g<S, FI, kGuidePassesMax, WPS, TEAM>(A, lds, threads, stream);
-}
-
-template <class S, int WPS, bool TEAM = false>
-static hipError_t launch_gls_f(const GlsArgs &A, size_t lds, int threads, bool first_improvement, hipStream_t stream) {
-    return first_improvement ? launch_gls_t<S, true, WPS, TEAM>(A, lds, threads, stream)
-                             : launch_gls_t<S, false, WPS, TEAM>(A, lds, threads, stream);
-}
-
-// 256-VGPR instantiation (two waves per SIMD) of the one-slot kernel: single-wavefront workgroups, n = 8 .. 33, best improvement
-bool gls_wps2_supported(int store, int penalty_bits, int n, int threads, bool first_improvement) {
-    return GLS_WPS2 && GLS_HALF_SCANS && !first_improvement && threads == kWave && n >= kHalfScanMinNodes && n <= kHalfScanMaxNodes &&
-           penalty_bits == 32 && (store == GLS_STORE_COMPACT || store == GLS_STORE_TRI);
-}
-
-// the serial perturbation phase runs in its edge form (serial_perturbation_edges) on the symmetric stores with 32-bit counters,
-// best improvement, the 128-VGPR and wider builds -- the host's copy of kEdgeForm in gls_kernel
-bool gls_edge_form(int store, int penalty_bits, int wps, bool team, bool first_improvement) {
-    return GLS_EDGE_PERTURB && store != GLS_STORE_GLOBAL && !(store == GLS_STORE_TRI && penalty_bits == 16) && !first_improvement && !team && wps <= 4;
-}
-
-bool gls_team_supported(int store, int penalty_bits, int wps, int n, int threads) {
-    // the team form exists for the 128-VGPR builds of the two symmetric stores with 32-bit counters, n <= 255; it caches the
-    // utilities of the tour edges by position on wavefronts 0 .. ceil(n / 64) - 1, so the workgroup needs that many
-    return (store == GLS_STORE_COMPACT || (store == GLS_STORE_TRI && penalty_bits == 32)) && wps == 4 && n >= 4 && n <= 255 &&
-           threads / kWave >= (n + kWave - 1) / kWave;
-}
-
-hipError_t launch_gls(const GlsArgs &A, int store, int penalty_bits, int threads, int wps, bool team, bool first_improvement,
-                      hipStream_t stream) {
-    if (team && !gls_team_supported(store, penalty_bits, wps, A.n, threads)) return hipErrorInvalidValue;
-    size_t lds = gls_lds_bytes(A.n, store, penalty_bits, team);
-#ifdef GLS_DEV_ONLY_HEADLINE
-    // development builds (ISA inspection, fast compiles): only the instantiation the TSP100 x 1024 headline runs on
-    (void)store; (void)penalty_bits; (void)wps; (void)first_improvement;
-    return launch_gls_k<TriDGlobalP, false, GLS_DEV_ONLY_HEADLINE + 0 == 4 ? 4 : 2, false, 4, false>(A, lds, threads, stream);   // (-DGLS_DEV_ONLY_HEADLINE=4: TSP200's)
-#else
-#if GLS_WPS2
-    if (wps == 2) {          // single-wavefront workgroups on the 256-VGPR build (gls_wps2_supported)
-        if (!gls_wps2_supported(store, penalty_bits, A.n, threads, first_improvement) || team) return hipErrorInvalidValue;
-        if (store == GLS_STORE_COMPACT) return launch_gls_g<TriDGlobalP, false, 1, 2, false>(A, lds, threads, stream);
-        return launch_gls_g<TriStore<int32_t>, false, 1, 2, false>(A, lds, threads, stream);
-    }
-#endif
-    if (store == GLS_STORE_COMPACT) {
-        if (team) return launch_gls_f<TriDGlobalPF, 4, true>(A, lds, threads, first_improvement, stream);
-        return wps == 8 ? launch_gls_f<TriDGlobalP, 8>(A, lds, threads, first_improvement, stream)
-                        : launch_gls_f<TriDGlobalP, 4>(A, lds, threads, first_improvement, stream);
-    }
-    if (store == GLS_STORE_TRI && penalty_bits == 16)
-        return launch_gls_f<TriStore<uint16_t>, TriStore<uint16_t>::kWavesPerSimd>(A, lds, threads, first_improvement, stream);
-    if (store == GLS_STORE_TRI) {
-        if (team) return launch_gls_f<TriStore<int32_t>, 4, true>(A, lds, threads, first_improvement, stream);
-        return wps == 4 ? launch_gls_f<TriStore<int32_t>, 4>(A, lds, threads, first_improvement, stream)
-                        : launch_gls_f<TriStore<int32_t>, TriStore<int32_t>::kWavesPerSimd>(A, lds, threads, first_improvement, stream);
-    }
-    return launch_gls_f<GlobalStore, GlobalStore::kWavesPerSimd>(A, lds, threads, first_improvement, stream);
-#endif
-}
-
-// registers and scratch of the instantiation launch_gls would run for these arguments (hipFuncGetAttributes: needs the device)
-hipError_t gls_kernel_resources(const GlsArgs &A, int store, int penalty_bits, int threads, int wps, bool team, bool first_improvement,
-                                int *vgprs, int *scratch_bytes) {
-    const void *fn = nullptr;
-    t_query_fn = &fn;
-    const hipError_t e = launch_gls(A, store, penalty_bits, threads, wps, team, first_improvement, nullptr);
-    t_query_fn = nullptr;
-    if (e != hipSuccess) return e;
+hipError_t gls_kernel_resources(const GlsPlan &p, int *vgprs, int *scratch_bytes) {
+    const void *fn = gls_kernel_fn(p);
     if (!fn) return hipErrorInvalidValue;
     hipFuncAttributes at;
-    const hipError_t e2 = hipFuncGetAttributes(&at, fn);
-    if (e2 != hipSuccess) return e2;
+    const hipError_t e = hipFuncGetAttributes(&at, fn);
+    if (e != hipSuccess) return e;
     if (vgprs) *vgprs = at.numRegs;
     if (scratch_bytes) *scratch_bytes = (int)at.localSizeBytes;
     return hipSuccess;
-}
-
-// executed-evaluation counting (measurement hook) exists where gls_count_supported says; elsewhere a run that prunes cannot
-// report it
-bool gls_count_supported(int store, int wps, int n, bool first_improvement, bool trace) {
-    (void)n;
-    return store == GLS_STORE_COMPACT && wps == 4 && !first_improvement && !trace;
-}
-
-// pruned descent scans exist in the 4-slot instantiations of the symmetric stores (n >= 128), best improvement only; the
-// lists must be full (n - 1 >= 32)
-bool gls_prune_supported(int store, int n, bool first_improvement, int wps) {
-    return store != GLS_STORE_GLOBAL && !first_improvement && n >= kPruneMinNodes && n <= 255 && wps <= GLS_PRUNE_MAX_WPS;
 }
 
 hipError_t launch_symmetry_check(const double *D, int B, int n, int32_t *asym, hipStream_t stream) {
@@ -1019,9 +897,9 @@ hipError_t launch_delta_all(const int32_t *tour, const double *D, int B, int n, 
 }
 
 hipError_t launch_best_move(const int32_t *tour, const double *D, int B, int n, int op, const int32_t *pos_i,
-                            bool first_improvement, double *delta_out, int32_t *move_out, int32_t *new_tour,
+                            bool first_improvement, int threads, double *delta_out, int32_t *move_out, int32_t *new_tour,
                             hipStream_t stream) {
-    int threads = pos_i ? 64 : gls_block_threads(n, GLS_STORE_GLOBAL);
+    if (pos_i) threads = 64;
     (void)hipGetLastError();
     if (first_improvement)
         hipLaunchKernelGGL(best_move_kernel<true>, dim3(B), dim3(threads), 0, stream, tour, D, n, op, pos_i, delta_out, move_out, new_tour);

@@ -437,9 +437,6 @@ __device__ __forceinline__ void team_perturbation(const S &s, const double k, TT
                                       // (profiles/r05_experiments/ab_edge_unrolled_and_prefetch.log, bit-exact): -1 % at TSP100 x 1024,
                                       // -8 % at TSP20 / TSP50 against the same unrolled step without it -- off
 #endif
-#ifndef GLS_EDGE_PERTURB
-#define GLS_EDGE_PERTURB 1           // 0: the scan-by-scan serial form everywhere (A/B builds)
-#endif
 
 template <int GP>
 struct TourEdges {

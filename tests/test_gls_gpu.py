@@ -290,6 +290,64 @@ def test_gls_global_store_fallback(ops):
         assert r.best_tour[b].cpu().tolist() == o["best_tour"]
 
 
+# One row per family of instantiations the launch plan can select (csrc/gls_kernels.hip: gls_kernel_fn): the smallest shape
+# that selects it.  id: (n, B, penalty_bits, first_improvement, trace, team override,
+#      expected gls_describe_run: store, threads, waves_per_simd, team, edge_form; run against the oracle here)
+# (the rows without a run of their own are driven against the oracle by the tests around this one)
+PLAN_ROWS = {
+    "compact-256vgpr-one-slot": (20, 1000, -2, False, False, -1, ("compact", 64, 2, False, True), False),
+    "lds-256vgpr-one-slot": (20, 1000, 0, False, False, -1, ("lds-tri-i32", 64, 2, False, True), False),
+    "compact-64vgpr": (20, 5000, -2, False, False, -1, ("compact", 64, 8, False, False), True),
+    "lds-80vgpr": (20, 5000, 0, False, False, -1, ("lds-tri-i32", 64, 6, False, False), True),
+    "compact-128vgpr-one-slot": (50, 8, -2, False, False, -1, ("compact", 256, 4, False, True), True),
+    "lds-128vgpr-one-slot": (50, 8, 0, False, False, -1, ("lds-tri-i32", 256, 4, False, True), False),
+    "compact-128vgpr-two-slot": (100, 1024, 0, False, False, -1, ("compact", 256, 4, False, True), False),
+    "compact-128vgpr-two-slot-trace": (100, 1024, 0, False, True, -1, ("compact", 256, 4, False, True), False),
+    "compact-128vgpr-two-slot-first-improvement": (100, 1024, 0, True, False, -1, ("compact", 256, 4, False, False), False),
+    "compact-128vgpr-four-slot": (200, 256, 0, False, False, -1, ("compact", 1024, 4, False, True), False),
+    "lds-128vgpr": (100, 256, 0, False, False, -1, ("lds-tri-i32", 512, 4, False, True), False),
+    "lds-u16-80vgpr": (100, 700, 16, False, False, -1, ("lds-tri-u16", 512, 6, False, False), False),
+    "compact-team": (150, 8, -2, True, False, -1, ("compact", 1024, 4, True, False), False),
+    "lds-team": (100, 8, 0, False, False, 1, ("lds-tri-i32", 512, 4, True, False), False),
+    "global": (300, 8, 0, False, False, -1, ("global", 512, 4, False, False), False),
+}
+
+
+@pytest.mark.parametrize("row", list(PLAN_ROWS))
+def test_plan_selects_the_recorded_instantiation(ops, row):
+    """The plan of the row's shape is the one written in the row, and the kernel it selects has the registers and scratch
+    that the instantiation of the same shape had before the launch policy became one function (golden/gls_kernel_resources.json,
+    recorded on an MI355X at the commit named there; the query launches nothing).  Families that no other test drives
+    against the oracle run here: the whole batch for three outer iterations, a sample of 32 instances compared bit for bit."""
+    import json
+    from oracle import gls_oracle as go
+    n, B, bits, fi, trace, team, want, run = PLAN_ROWS[row]
+    with open(os.path.join(GOLD, "gls_kernel_resources.json")) as f:
+        recorded = json.load(f)["rows"][row]
+    with ops.gls_team_mode(team):
+        d = ops.gls_describe_run(n, B, bits, fi)
+        assert (d["store"], d["threads"], d["waves_per_simd"], d["team"], d["edge_form"]) == want
+        assert ops.gls_kernel_resources(n, B, bits, fi, trace) == recorded
+    if not run:
+        return
+    K = 3
+    D, _ = random_instances(np.random.default_rng(9000 + n + B), B, n)
+    dd = dev(D, torch.float64)
+    init = ops.nearest_neighbor(dd)
+    cost = ops.tour_cost(init, dd)
+    r = ops.gls_run(dd, dd[None].contiguous(), init, cost, perturbation_moves=20, first_improvement=fi, max_outer_iters=K,
+                    trace_cap=64 if trace else 0, want_penalty=True, penalty_bits=bits)
+    assert (r.status == 0).all() and (r.outer_iters == K).all()
+    init_h, cost_h = init.cpu().numpy(), cost.cpu().numpy()
+    for b in np.linspace(0, B - 1, min(B, 32)).astype(int):
+        o = go.guided_local_search(D[b], D[b][None], init_h[b], cost_h[b], perturbation_moves=20, first_improvement=fi,
+                                   max_outer_iters=K)
+        assert r.best_tour[b].cpu().tolist() == o["best_tour"]
+        assert_bits(r.best_cost[b].item(), o["best_cost"])
+        assert np.array_equal(r.penalty[b].cpu().numpy(), o["penalty"])
+        assert int(r.evals[b]) == o["evals"] and int(r.trace_len[b]) == o["trace_len"]
+
+
 def test_gls_time_mode_and_properties(ops):
     """Wall-clock mode at TSP100: valid tours, cost == tour_cost(best_tour), never worse than the
     local-search-only result, and the deterministic K-iteration trace is a prefix of a longer run."""
