@@ -5,7 +5,8 @@
 hipcc cross-compiles without a GPU.  The .so is kept in-tree (gnngls_amd/libgnngls_hip.so,
 git-ignored) so that it travels with the repo snapshot to the GPU box.  Every translation unit is
 compiled to an object of its own (gnngls_amd/build/*.o, git-ignored), stale ones in parallel, then
-linked: the search kernels take ~90 s, the other units seconds each (gls_plan.cpp, the launch plan, is plain host C++).
+linked: the search kernels take ~90 s, the other units seconds each (gls_plan.cpp and model_plan.cpp, the launch plans, are plain
+host C++).
 """
 import os
 import subprocess
@@ -16,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 SO = os.path.join(HERE, "libgnngls_hip.so")
-SOURCES = ["gls_kernels.hip", "gls_plan.cpp", "model_kernels.hip", "train_kernels.hip", "heads_kernels.hip", "labels_kernels.hip", "constructors_kernels.hip",
+SOURCES = ["gls_kernels.hip", "gls_plan.cpp", "model_kernels.hip", "model_plan.cpp", "train_kernels.hip", "heads_kernels.hip", "labels_kernels.hip", "constructors_kernels.hip",
            "bounds_kernels.hip", "capi.hip"]
 # -ffp-contract=off: the guided matrix D + k*P (gnngls/algorithms.py:164) rounds twice and np.isclose
 # (operators.py:42) is evaluated literally; a fused multiply-add would change move selection.
@@ -25,14 +26,15 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 HEADERS = {
     "gls_kernels.hip": ["gls_common.h", "gls_descent_scans.h", "gls_perturbation.h", "gls_kernels.h", "gls_plan.h", "gls_policy.h"],
     "gls_plan.cpp": ["gls_plan.h", "gls_policy.h"],
-    "model_kernels.hip": ["model_kernels.h"],
+    "model_kernels.hip": ["model_kernels.h", "model_plan.h", "model_policy.h"],
+    "model_plan.cpp": ["model_plan.h", "model_policy.h", os.path.join("..", "..", "include", "gnngls_hip.h")],
     "train_kernels.hip": ["train_kernels.h", "model_kernels.h"],
-    "heads_kernels.hip": ["heads_kernels.h"],
+    "heads_kernels.hip": ["heads_kernels.h", "model_policy.h"],
     "labels_kernels.hip": ["labels_kernels.h", "gls_kernels.h", "gls_plan.h", "gls_policy.h"],
     "constructors_kernels.hip": ["constructors_kernels.h", "gls_common.h", "gls_policy.h"],
     "bounds_kernels.hip": ["bounds_kernels.h", "gls_common.h", "gls_policy.h"],
-    "capi.hip": ["gls_kernels.h", "gls_plan.h", "gls_policy.h", "model_kernels.h", "train_kernels.h", "heads_kernels.h", "labels_kernels.h", "constructors_kernels.h",
-                 "bounds_kernels.h", os.path.join("..", "..", "include", "gnngls_hip.h")],
+    "capi.hip": ["gls_kernels.h", "gls_plan.h", "gls_policy.h", "model_kernels.h", "model_plan.h", "model_policy.h", "train_kernels.h", "heads_kernels.h",
+                 "labels_kernels.h", "constructors_kernels.h", "bounds_kernels.h", os.path.join("..", "..", "include", "gnngls_hip.h")],
 }
 
 

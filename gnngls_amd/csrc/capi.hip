@@ -19,6 +19,7 @@
 #include "heads_kernels.h"
 #include "labels_kernels.h"
 #include "model_kernels.h"
+#include "model_plan.h"
 #include "train_kernels.h"
 
 namespace {
@@ -486,41 +487,49 @@ int gnngls_regret_labels(const double *D, int B, int n, const int32_t *base_tour
 // GNN forward
 // ---------------------------------------------------------------------------------------------
 namespace {
-constexpr long kLayerFloats = 128L * 128 + 128 + 128 + 128 + 128 + 512L * 128 + 512 + 128L * 512 + 128 + 128 + 128;
-// the parameters of one layer inside the packed weights (and, with T = float, of their gradients): models.py:20-36
+using gnngls::kModelLdsPerCU;
+// the parameters of one layer inside the packed weights (and, with T = float, of their gradients)
 template <typename T>
 struct LayerParams { T *fc_w, *attn_l, *attn_r, *bn1_g, *bn1_b, *w1, *b1, *w2, *b2, *bn2_g, *bn2_b; };
 template <typename T>
-LayerParams<T> layer_params(T *w) {
-    LayerParams<T> p;
-    p.fc_w = w; p.attn_l = p.fc_w + 128L * 128; p.attn_r = p.attn_l + 128; p.bn1_g = p.attn_r + 128; p.bn1_b = p.bn1_g + 128;
-    p.w1 = p.bn1_b + 128; p.b1 = p.w1 + 512L * 128; p.w2 = p.b1 + 512; p.b2 = p.w2 + 128L * 512; p.bn2_g = p.b2 + 128; p.bn2_b = p.bn2_g + 128;
-    return p;
+LayerParams<T> layer_params(T *w, const gnngls::PackedModel &m, int l) {
+    const gnngls::LayerOffsets o = m.layer(l);
+    return {w + o.fc_w, w + o.attn_l, w + o.attn_r, w + o.bn1_g, w + o.bn1_b, w + o.w1, w + o.b1, w + o.w2, w + o.b2, w + o.bn2_g, w + o.bn2_b};
 }
 #define GNNGLS_TRY(x) do { e = (x); if (e != hipSuccess) return hip_fail(e, #x); } while (0)
 
-constexpr long kBytesPerNode = (128 + 128 + 256 + 32 + 128) * 4L;   // h, ft, part, part_ms, h2 (ping-pong)
-// 16 heads: + the per-head softmax statistics of both sides [2][16 + 16] (gat_heads_merge16_kernel's input)
-long bytes_per_node(int n_heads) { return kBytesPerNode + (n_heads == 16 ? 2 * 32 * 4L : 0); }
+// the experiment switches (A/B runs), read once per process: the only place of the model's code that looks at the environment
+const gnngls::ForwardSwitches &forward_switches() {
+    static const gnngls::ForwardSwitches sw = [] {
+        gnngls::ForwardSwitches v;
+        const char *fp32 = getenv("GNNGLS_FFN_FP32"), *rank1 = getenv("GNNGLS_GAT_RANK1"), *heads = getenv("GNNGLS_GAT_HEADS");
+        v.ffn_fp32 = fp32 && atoi(fp32) != 0;
+        v.rank1_mode = rank1 && atoi(rank1) == 0 ? 0 : rank1 && atoi(rank1) == 2 ? 2 : -1;
+        v.gat_heads = !heads ? 0 : atoi(heads) == 4 ? 4 : 8;       // (set to anything but 4: the unsplit form)
+        return v;
+    }();
+    return sw;
+}
 
 int heads_fail(const char *what, int n_heads) {
     return fail(GNNGLS_ERR_UNSUPPORTED, "%s: n_heads=%d is not supported (embed_dim 128: n_heads in {1, 2, 4, 8, 16})", what, n_heads);
 }
+
+unsigned char *align256(const void *p) { return (unsigned char *)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
 }  // namespace
 
 extern "C" {
 
 int64_t gnngls_model_packed_floats(int in_dim, int n_layers) {
     if (in_dim < 0 || n_layers < 0) return 0;
-    return 128L * in_dim + 128 + (long)n_layers * kLayerFloats + 128 + 4;
+    return gnngls::packed_model(in_dim, n_layers).total;
 }
 
 int64_t gnngls_regret_forward_workspace_bytes(int B, int n) { return gnngls_regret_forward_workspace_bytes_heads(B, n, 8); }
 
 int64_t gnngls_regret_prepared_bytes(int n_layers) {
     if (n_layers < 0) return 0;
-    // per layer the feed-forward weights in bf16 pieces; behind them A = We^T Wfc^T and b' = Wfc be of the fused embed + first fc
-    return (int64_t)n_layers * (int64_t)gnngls::ffn_packed_bytes() + (int64_t)gnngls::embed_fc_bytes() + 256;
+    return (int64_t)gnngls::prepared_bytes(n_layers);
 }
 
 int gnngls_regret_prepare(const float *weights, int in_dim, int n_layers, void *prepared, int64_t prepared_bytes, void *stream) {
@@ -528,18 +537,18 @@ int gnngls_regret_prepare(const float *weights, int in_dim, int n_layers, void *
     if (prepared_bytes < gnngls_regret_prepared_bytes(n_layers))
         return fail(GNNGLS_ERR_ARG, "regret_prepare: buffer too small (%lld B, need %lld B)", (long long)prepared_bytes,
                     (long long)gnngls_regret_prepared_bytes(n_layers));
-    unsigned char *base = (unsigned char *)(((uintptr_t)prepared + 255) & ~(uintptr_t)255);
-    const float *layers = weights + 128L * in_dim + 128;
+    unsigned char *base = align256(prepared);
+    const gnngls::PackedModel m = gnngls::packed_model(in_dim, n_layers);
     for (int l = 0; l < n_layers; ++l) {
-        const LayerParams<const float> p = layer_params(layers + (long)l * kLayerFloats);
-        const float *fc_next = l + 1 < n_layers ? layers + (long)(l + 1) * kLayerFloats : nullptr;
-        hipError_t e = gnngls::launch_ffn_pack(p.w1, p.w2, fc_next, base + (size_t)l * gnngls::ffn_packed_bytes(), (hipStream_t)stream);
+        const LayerParams<const float> p = layer_params(weights, m, l);
+        const float *fc_next = l + 1 < n_layers ? weights + m.layer(l + 1).fc_w : nullptr;
+        hipError_t e = gnngls::launch_ffn_pack(p.w1, p.w2, fc_next, base + gnngls::prepared_layer(l), (hipStream_t)stream);
         if (e != hipSuccess) return hip_fail(e, "regret_prepare");
     }
-    if (n_layers > 0 && in_dim <= gnngls::embed_fc_max_in_dim()) {
-        const LayerParams<const float> p = layer_params(layers);
-        hipError_t e = gnngls::launch_embed_fc_prepare(weights, weights + 128L * in_dim, p.fc_w, p.attn_l, p.attn_r,
-                                                       in_dim, base + (size_t)n_layers * gnngls::ffn_packed_bytes(), (hipStream_t)stream);
+    if (n_layers > 0 && in_dim <= gnngls::kEmbedFcMaxIn) {
+        const LayerParams<const float> p = layer_params(weights, m, 0);
+        hipError_t e = gnngls::launch_embed_fc_prepare(weights + m.emb_w, weights + m.emb_b, p.fc_w, p.attn_l, p.attn_r, in_dim,
+                                                       base + gnngls::prepared_embed_fc(n_layers), (hipStream_t)stream);
         if (e != hipSuccess) return hip_fail(e, "regret_prepare");
     }
     return GNNGLS_OK;
@@ -548,116 +557,94 @@ int gnngls_regret_prepare(const float *weights, int in_dim, int n_layers, void *
 }  // extern "C"
 
 namespace {
-int forward_prepared_impl(const float *feat, const float *weights, const void *prepared, int64_t prepared_bytes, int B, int n,
-                          int in_dim, int n_layers, int n_heads, float *y_out, void *workspace, int64_t workspace_bytes,
-                          void *stream) {
-    if (B == 0) return GNNGLS_OK;   // empty batch: nothing to enqueue (data pointers may be NULL)
-    if (!feat || !weights || !y_out || !workspace || B < 0 || n < 3 || in_dim < 1 || n_layers < 0)
-        return fail(GNNGLS_ERR_ARG, "regret_forward: bad argument");
-    if ((in_dim * 128) % 4 != 0) return fail(GNNGLS_ERR_UNSUPPORTED, "regret_forward: in_dim*128 must be a multiple of 4");
-    const bool h8 = n_heads == 8;
-    if (h8 && gnngls::gat_rows_lds_bytes(n) > kLdsPerCU)
-        return fail(GNNGLS_ERR_UNSUPPORTED, "regret_forward: n=%d needs %zu B of LDS per row tile (> 160 KiB)", n,
-                    gnngls::gat_rows_lds_bytes(n));
-    if (!h8 && n > gnngls::heads_max_nodes())
-        return fail(GNNGLS_ERR_UNSUPPORTED, "regret_forward: n=%d exceeds the %d-head attention tile limit (n <= %d; 8 heads: n <= 423)", n,
-                    n_heads, gnngls::heads_max_nodes());
-    // prepared == NULL keeps the feed-forward block on the fp32 matrix pipe (as GNNGLS_FFN_FP32=1 does: A/B runs)
-    static const bool ffn_fp32 = getenv("GNNGLS_FFN_FP32") && atoi(getenv("GNNGLS_FFN_FP32")) != 0;
-    if (prepared && prepared_bytes < gnngls_regret_prepared_bytes(n_layers))
-        return fail(GNNGLS_ERR_ARG, "regret_forward: prepared image too small (%lld B, need %lld B)", (long long)prepared_bytes,
-                    (long long)gnngls_regret_prepared_bytes(n_layers));
-    const unsigned char *prep = (prepared && !ffn_fp32) ? (const unsigned char *)(((uintptr_t)prepared + 255) & ~(uintptr_t)255) : nullptr;
-    const long N = (long)n * (n - 1) / 2;
-    uintptr_t base = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    int64_t avail = workspace_bytes - (int64_t)(base - (uintptr_t)workspace);
-    long Bc = avail / (N * bytes_per_node(n_heads));
-    if (Bc < 1) return fail(GNNGLS_ERR_ARG, "regret_forward: workspace too small (%lld B, need >= %lld B)",
-                            (long long)workspace_bytes, (long long)gnngls_regret_forward_workspace_bytes_heads(1, n, n_heads));
-    if (Bc > B) Bc = B;
-    hipStream_t st = (hipStream_t)stream;
-    const long Mc = Bc * N;
-    float *h = (float *)base;
-    float *ft = h + Mc * 128;
-    float *part = ft + Mc * 128;
-    float *part_ms = part + 2 * Mc * 128;
-    float *h2 = part_ms + 2 * Mc * 16;
-    float *hms = h2 + Mc * 128;                          // (16 heads) [2][Mc][32]
-    const float *emb_w = weights, *emb_b = weights + 128L * in_dim;
-    const float *layers = emb_b + 128;
-    const float *dec_w = layers + (long)n_layers * kLayerFloats, *dec_b = dec_w + 128;
-    hipError_t e = hipSuccess;
-    for (long b0 = 0; b0 < B; b0 += Bc) {
-        const int bc = (int)((B - b0) < Bc ? (B - b0) : Bc);
-        const long M = (long)bc * N;
-        // models.py:66; with a prepared image also ft = fc(h) of layer 0 (models.py:23), both straight from the input features
-        const bool fused_fc0 = prep && n_layers > 0 && in_dim <= gnngls::embed_fc_max_in_dim();
-        static const bool no_rank1 = getenv("GNNGLS_GAT_RANK1") && atoi(getenv("GNNGLS_GAT_RANK1")) == 0;      // (A/B runs)
-        const bool rank1_gat0 = fused_fc0 && in_dim == 1 && n <= 255 && !no_rank1 && h8;     // (its image holds 8-head coefficients)
-        // ... and then the first feed-forward launch forms its input from the one feature and the compact partials (LR0): no embedding
-        // pass at all, neither h_0 nor ft_0 nor 128-wide partials of the first layer in memory (GNNGLS_GAT_RANK1=2: keep them, A/B runs)
-        static const bool keep_h0 = getenv("GNNGLS_GAT_RANK1") && atoi(getenv("GNNGLS_GAT_RANK1")) == 2;
-        const bool lr0 = rank1_gat0 && !keep_h0;
-        const float *img0 = (const float *)(prep ? prep + (size_t)n_layers * gnngls::ffn_packed_bytes() : nullptr);
-        if (!lr0) { ProfScope ps(GNNGLS_PROF_EMBED, st);
-          // (one input feature: the first GATConv runs in its rank-1 form below and no ft is written)
-          if (fused_fc0) GNNGLS_TRY(gnngls::launch_embed_fc(feat + b0 * N * in_dim, emb_w, emb_b, prep + (size_t)n_layers * gnngls::ffn_packed_bytes(), h,
-                                                            rank1_gat0 ? nullptr : ft, M, in_dim, st));
-          else GNNGLS_TRY(gnngls::launch_embed(feat + b0 * N * in_dim, emb_w, emb_b, h, M, in_dim, st)); }
-        for (int l = 0; l < n_layers; ++l) {                                                          // models.py:67-68
-            const LayerParams<const float> p = layer_params(layers + (long)l * kLayerFloats);
-            // ft = fc(h), models.py:23: a launch of its own for the first layer (and for every layer on the fp32 path); on the bf16x3 path
-            // the feed-forward launch of layer l - 1 has already written it (fc folded into that kernel's tail)
-            if ((l == 0 && !fused_fc0) || !prep) {
-              ProfScope ps(GNNGLS_PROF_GEMM_FC, st);
-              GNNGLS_TRY(gnngls::launch_gemm(gnngls::GEMM_EPI_STORE, h, p.fc_w, ft, M, 128, 128, nullptr, nullptr, nullptr, nullptr, st)); }
-            if (l == 0 && rank1_gat0) {
-              ProfScope ps(GNNGLS_PROF_GAT_ROWS_RANK1, st);
-              GNNGLS_TRY(gnngls::launch_gat_rows_rank1(feat + b0 * N, prep + (size_t)n_layers * gnngls::ffn_packed_bytes(), bc, n, part, part_ms, st, lr0));
-            } else if (h8) {
-              ProfScope ps(GNNGLS_PROF_GAT_ROWS, st);
-              GNNGLS_TRY(gnngls::launch_gat_rows(ft, p.attn_l, p.attn_r, bc, n, part, part_ms, st));
-            } else {
-              ProfScope ps(GNNGLS_PROF_GAT_ROWS, st);
-              GNNGLS_TRY(gnngls::launch_gat_heads_rows(ft, p.attn_l, p.attn_r, bc, n, n_heads, part, part_ms, hms, st));
-              if (n_heads == 16) GNNGLS_TRY(gnngls::launch_gat_heads_merge16(part, hms, part_ms, M, st)); }
-            // gat_combine + FFN1 + FFN2 (+ the next layer's fc) in one launch; the hidden layer and x = BN1(h + GAT) never touch HBM
-            { ProfScope ps(GNNGLS_PROF_FFN_FUSED, st);
-              // (the last layer's launch also applies the decision layer, models.py:69: its output is never stored)
-              const bool last = prep && l + 1 == n_layers;
-              const bool lr = l == 0 && lr0;
-              GNNGLS_TRY(gnngls::launch_ffn_fused(part, part_ms, lr ? feat + b0 * N : h, p.bn1_g, p.bn1_b, p.w1, p.b1, p.w2, p.b2, p.bn2_g, p.bn2_b, h2, M,
-                                                  prep ? prep + (size_t)l * gnngls::ffn_packed_bytes() : nullptr, prep && l + 1 < n_layers, ft, st,
-                                                  last ? dec_w : nullptr, last ? dec_b : nullptr, last ? y_out + b0 * N : nullptr,
-                                                  lr ? img0 : nullptr, lr ? emb_w : nullptr, lr ? emb_b : nullptr)); }
-            { float *x = h; h = h2; h2 = x; }
-        }
-        if (!(prep && n_layers > 0)) {
-          ProfScope ps(GNNGLS_PROF_DECISION, st);
-          GNNGLS_TRY(gnngls::launch_decision(h, dec_w, dec_b, y_out + b0 * N, M, st)); }               // models.py:69
-    }
-    return GNNGLS_OK;
+// the attention of one layer as the plan (or, for the training step, gat_rows_step / gat_heads_rows_step) shaped it
+hipError_t launch_attention(const gnngls::AttnStep &a, const float *ft, const float *attn_l, const float *attn_r, int B, int n,
+                            float *part, float *part_ms, float *hms, hipStream_t st) {
+    if (a.form == gnngls::ATTN_K1) return gnngls::launch_gat_rows(ft, attn_l, attn_r, B, n, a.heads_per_wg, a.waves, part, part_ms, st);
+    return gnngls::launch_gat_heads_rows(ft, attn_l, attn_r, B, n, gnngls::kD / a.F, a.waves, part, part_ms, hms, st);
 }
 
-// The one-call form: splits the weights into stream-ordered scratch of its own on every call (gnngls_regret_prepare +
+// Every forward entry point: makes the request, takes the plan (model_plan.cpp), and executes its steps chunk by chunk.
+// one_call: no image from the caller -- the weights are split into stream-ordered scratch of this call (gnngls_regret_prepare +
 // gnngls_regret_forward_prepared keep the image across calls: 2 launches per layer and the allocation saved per forward).
-int forward_one_call(const float *feat, const float *weights, int B, int n, int in_dim, int n_layers, int n_heads,
-                     float *y_out, void *workspace, int64_t workspace_bytes, void *stream) {
-    if (B == 0) return GNNGLS_OK;
-    if (!feat || !weights || !y_out || !workspace || B < 0 || n < 3 || in_dim < 1 || n_layers < 0)
-        return fail(GNNGLS_ERR_ARG, "regret_forward: bad argument");
-    if (n_heads != 8 && n > gnngls::heads_max_nodes())        // (before the scratch image is made)
-        return forward_prepared_impl(feat, weights, nullptr, 0, B, n, in_dim, n_layers, n_heads, y_out, workspace, workspace_bytes, stream);
-    StreamScratch ffn_ws((hipStream_t)stream);
-    static const bool ffn_fp32 = getenv("GNNGLS_FFN_FP32") && atoi(getenv("GNNGLS_FFN_FP32")) != 0;
-    const int64_t pb = gnngls_regret_prepared_bytes(n_layers);
-    if (n_layers > 0 && !ffn_fp32) {
-        hipError_t e = ffn_ws.alloc((size_t)pb);
+int run_forward(bool one_call, const float *feat, const float *weights, const void *prepared, int64_t prepared_bytes, int B, int n,
+                int in_dim, int n_layers, int n_heads, float *y_out, void *workspace, int64_t workspace_bytes, void *stream) {
+    unsigned char *base = align256(workspace);
+    const gnngls::ForwardPlan plan = gnngls::forward_plan({n, B, in_dim, n_layers, n_heads, feat && weights && y_out && workspace, one_call,
+                                                           prepared != nullptr, prepared_bytes,
+                                                           workspace_bytes - (int64_t)(base - (unsigned char *)workspace), forward_switches()});
+    hipStream_t st = (hipStream_t)stream;
+    StreamScratch scratch(st);
+    if (plan.build_image) {
+        prepared_bytes = gnngls_regret_prepared_bytes(n_layers);
+        hipError_t e = scratch.alloc((size_t)prepared_bytes);
         if (e != hipSuccess) return hip_fail(e, "regret_forward: scratch alloc");
-        const int rc = gnngls_regret_prepare(weights, in_dim, n_layers, ffn_ws.p, pb, stream);
+        const int rc = gnngls_regret_prepare(weights, in_dim, n_layers, scratch.p, prepared_bytes, stream);
         if (rc != GNNGLS_OK) return rc;
+        prepared = scratch.p;
     }
-    return forward_prepared_impl(feat, weights, ffn_ws.p, pb, B, n, in_dim, n_layers, n_heads, y_out, workspace, workspace_bytes, stream);
+    switch (plan.why) {
+    case gnngls::FWD_OK: break;
+    case gnngls::FWD_BAD_HEADS: return heads_fail("regret_forward", n_heads);
+    case gnngls::FWD_BAD_ARG: return fail(plan.status, "regret_forward: bad argument");
+    case gnngls::FWD_K1_LDS:
+        return fail(plan.status, "regret_forward: n=%d needs %zu B of LDS per row tile (> 160 KiB)", n, (size_t)plan.number);
+    case gnngls::FWD_K1H_NODES:
+        return fail(plan.status, "regret_forward: n=%d exceeds the %d-head attention tile limit (n <= %d; 8 heads: n <= 423)", n, n_heads,
+                    (int)plan.number);
+    case gnngls::FWD_IMAGE_SMALL:
+        return fail(plan.status, "regret_forward: prepared image too small (%lld B, need %lld B)", (long long)prepared_bytes,
+                    (long long)plan.number);
+    case gnngls::FWD_WORKSPACE_SMALL:
+        return fail(plan.status, "regret_forward: workspace too small (%lld B, need >= %lld B)", (long long)workspace_bytes,
+                    (long long)plan.number);
+    }
+    if (plan.Bc == 0) return GNNGLS_OK;   // empty batch: nothing to enqueue (data pointers may be NULL)
+    const gnngls::PackedModel m = gnngls::packed_model(in_dim, n_layers);
+    const unsigned char *image = plan.use_image ? align256(prepared) : nullptr;
+    const float *img0 = (const float *)(image ? image + gnngls::prepared_embed_fc(n_layers) : nullptr);      // the embed-fc image
+    const long N = (long)n * (n - 1) / 2;
+    float *h = (float *)(base + plan.ws.h), *ft = (float *)(base + plan.ws.ft), *part = (float *)(base + plan.ws.part);
+    float *part_ms = (float *)(base + plan.ws.part_ms), *h2 = (float *)(base + plan.ws.h2), *hms = (float *)(base + plan.ws.hms);
+    const float *emb_w = weights + m.emb_w, *emb_b = weights + m.emb_b, *dec_w = weights + m.dec_w, *dec_b = weights + m.dec_b;
+    hipError_t e = hipSuccess;
+    for (long b0 = 0; b0 < B; b0 += plan.Bc) {
+        const int bc = (int)((B - b0) < plan.Bc ? (B - b0) : plan.Bc);
+        const long M = (long)bc * N;
+        const float *x = feat + b0 * N * in_dim;
+        if (plan.embed != gnngls::EMBED_NONE) {                                                       // models.py:66
+          ProfScope ps(GNNGLS_PROF_EMBED, st);
+          if (plan.embed == gnngls::EMBED_PLAIN) GNNGLS_TRY(gnngls::launch_embed(x, emb_w, emb_b, h, M, in_dim, st));
+          else GNNGLS_TRY(gnngls::launch_embed_fc(x, emb_w, emb_b, img0, h, plan.embed == gnngls::EMBED_FC ? ft : nullptr, M, in_dim, st)); }
+        for (int l = 0; l < n_layers; ++l) {                                                          // models.py:67-68
+            const gnngls::LayerStep &step = plan.layer(l);
+            const LayerParams<const float> p = layer_params(weights, m, l);
+            if (step.fc_launch) {                                                                     // ft = fc(h), models.py:23
+              ProfScope ps(GNNGLS_PROF_GEMM_FC, st);
+              GNNGLS_TRY(gnngls::launch_gemm(gnngls::GEMM_EPI_STORE, h, p.fc_w, ft, M, 128, 128, nullptr, nullptr, nullptr, nullptr, st)); }
+            switch (step.attn.form) {
+            case gnngls::ATTN_RANK1: case gnngls::ATTN_RANK1_COMPACT: {
+              ProfScope ps(GNNGLS_PROF_GAT_ROWS_RANK1, st);
+              GNNGLS_TRY(gnngls::launch_gat_rows_rank1(x, img0, bc, n, part, part_ms, st, step.attn.form == gnngls::ATTN_RANK1_COMPACT));
+              break; }
+            case gnngls::ATTN_K1: case gnngls::ATTN_K1H: {
+              ProfScope ps(GNNGLS_PROF_GAT_ROWS, st);
+              GNNGLS_TRY(launch_attention(step.attn, ft, p.attn_l, p.attn_r, bc, n, part, part_ms, hms, st));
+              if (step.attn.merge16) GNNGLS_TRY(gnngls::launch_gat_heads_merge16(part, hms, part_ms, M, st));
+              break; }
+            }
+            // gat_combine + FFN1 + FFN2 in one launch; the hidden layer and x = BN1(h + GAT) never touch HBM
+            { ProfScope ps(GNNGLS_PROF_FFN_FUSED, st);
+              const gnngls::FfnFused a = {part, part_ms, step.ffn.rank1_input ? x : h, p.bn1_g, p.bn1_b, p.w1, p.b1, p.w2, p.b2, p.bn2_g, p.bn2_b,
+                                          h2, M, image ? image + gnngls::prepared_layer(l) : nullptr, ft, dec_w, dec_b, y_out + b0 * N, img0, emb_w, emb_b};
+              GNNGLS_TRY(gnngls::launch_ffn_fused(a, step.ffn, st)); }
+            { float *t = h; h = h2; h2 = t; }
+        }
+        if (plan.decision_launch) {                                                                   // models.py:69
+          ProfScope ps(GNNGLS_PROF_DECISION, st);
+          GNNGLS_TRY(gnngls::launch_decision(h, dec_w, dec_b, y_out + b0 * N, M, st)); }
+    }
+    return GNNGLS_OK;
 }
 }  // namespace
 
@@ -666,13 +653,12 @@ extern "C" {
 int gnngls_regret_forward_prepared(const float *feat, const float *weights, const void *prepared, int64_t prepared_bytes,
                                    int B, int n, int in_dim, int n_layers,
                                    float *y_out, void *workspace, int64_t workspace_bytes, void *stream) {
-    return forward_prepared_impl(feat, weights, prepared, prepared_bytes, B, n, in_dim, n_layers, 8, y_out, workspace, workspace_bytes,
-                                 stream);
+    return run_forward(false, feat, weights, prepared, prepared_bytes, B, n, in_dim, n_layers, 8, y_out, workspace, workspace_bytes, stream);
 }
 
 int gnngls_regret_forward(const float *feat, const float *weights, int B, int n, int in_dim, int n_layers,
                           float *y_out, void *workspace, int64_t workspace_bytes, void *stream) {
-    return forward_one_call(feat, weights, B, n, in_dim, n_layers, 8, y_out, workspace, workspace_bytes, stream);
+    return run_forward(true, feat, weights, nullptr, 0, B, n, in_dim, n_layers, 8, y_out, workspace, workspace_bytes, stream);
 }
 
 // ---- head counts other than 8 (embed_dim 128): the same forward with the attention of heads_kernels.hip ----------------------
@@ -681,8 +667,7 @@ int gnngls_model_heads_supported(int n_heads) { return gnngls::heads_supported(n
 int64_t gnngls_regret_forward_workspace_bytes_heads(int B, int n, int n_heads) {
     if (!gnngls::heads_supported(n_heads)) return 0;
     if (B < 1 || n < 2 || n > 65535) return 0;          // 65535 nodes x 2^31 instances still fits an int64
-    const long N = (long)n * (n - 1) / 2;
-    return (int64_t)B * N * bytes_per_node(n_heads) + 256;
+    return (int64_t)gnngls::forward_layout((long)B * ((long)n * (n - 1) / 2), n_heads).end + 256;
 }
 
 int gnngls_regret_prepare_heads(const float *weights, int in_dim, int n_layers, int n_heads, void *prepared, int64_t prepared_bytes,
@@ -695,15 +680,13 @@ int gnngls_regret_prepare_heads(const float *weights, int in_dim, int n_layers, 
 int gnngls_regret_forward_prepared_heads(const float *feat, const float *weights, const void *prepared, int64_t prepared_bytes,
                                          int B, int n, int in_dim, int n_layers, int n_heads,
                                          float *y_out, void *workspace, int64_t workspace_bytes, void *stream) {
-    if (!gnngls::heads_supported(n_heads)) return heads_fail("regret_forward", n_heads);
-    return forward_prepared_impl(feat, weights, prepared, prepared_bytes, B, n, in_dim, n_layers, n_heads, y_out, workspace,
-                                 workspace_bytes, stream);
+    return run_forward(false, feat, weights, prepared, prepared_bytes, B, n, in_dim, n_layers, n_heads, y_out, workspace, workspace_bytes,
+                       stream);
 }
 
 int gnngls_regret_forward_heads(const float *feat, const float *weights, int B, int n, int in_dim, int n_layers, int n_heads,
                                 float *y_out, void *workspace, int64_t workspace_bytes, void *stream) {
-    if (!gnngls::heads_supported(n_heads)) return heads_fail("regret_forward", n_heads);
-    return forward_one_call(feat, weights, B, n, in_dim, n_layers, n_heads, y_out, workspace, workspace_bytes, stream);
+    return run_forward(true, feat, weights, nullptr, 0, B, n, in_dim, n_layers, n_heads, y_out, workspace, workspace_bytes, stream);
 }
 
 int gnngls_pack_features(const double *D, int B, int n, double scale, double min_, float *feat, void *stream) {
@@ -790,13 +773,13 @@ int train_check(const char *what, const void *feat, const void *params, const vo
     if (n > gnngls::gat_bwd_max_nodes())
         return fail(GNNGLS_ERR_UNSUPPORTED, "%s: n=%d exceeds the attention-backward tile limit (n <= %d)", what, n,
                     gnngls::gat_bwd_max_nodes());
-    if (n_heads == 8 && (gnngls::gat_rows_lds_bytes(n) > kLdsPerCU || gnngls::gat_bwd_lds_bytes(n) > kLdsPerCU))
+    if (n_heads == 8 && (gnngls::gat_rows_lds_bytes(n) > kModelLdsPerCU || gnngls::gat_bwd_lds_bytes(n) > kModelLdsPerCU))
         return fail(GNNGLS_ERR_UNSUPPORTED, "%s: n=%d needs %zu B of LDS per row tile (> 160 KiB)", what, n,
                     gnngls::gat_bwd_lds_bytes(n));
-    if (n_heads != 8 && (n > gnngls::heads_max_nodes() || gnngls::gat_heads_rows_lds_bytes(n, n_heads) > kLdsPerCU ||
-                         gnngls::gat_heads_bwd_lds_bytes(n, n_heads) > kLdsPerCU))
+    if (n_heads != 8 && (n > gnngls::kMaxNodes || gnngls::gat_heads_rows_lds_bytes(n, n_heads) > kModelLdsPerCU ||
+                         gnngls::gat_heads_bwd_lds_bytes(n, n_heads) > kModelLdsPerCU))
         return fail(GNNGLS_ERR_UNSUPPORTED, "%s: n=%d exceeds the %d-head attention tile limit (n <= %d)", what, n, n_heads,
-                    gnngls::heads_max_nodes());
+                    gnngls::kMaxNodes);
     const int64_t need = gnngls_regret_train_workspace_bytes_heads(B, n, n_layers, n_heads);
     if (workspace_bytes < need)
         return fail(GNNGLS_ERR_ARG, "%s: workspace too small (%lld B, need %lld B)", what, (long long)workspace_bytes,
@@ -833,8 +816,9 @@ int gnngls_regret_train_forward_heads(const float *feat, const float *params, in
     const long N = (long)n * (n - 1) / 2, M = (long)B * N;
     const int stat_w = n_heads == 16 ? 32 : 16;
     const TrainWs w = train_layout((uintptr_t)workspace, M, n_layers, stat_w);
-    const float *emb_w = params, *emb_b = params + 128L * in_dim, *layers = emb_b + 128;
-    const float *dec_w = layers + (long)n_layers * kLayerFloats, *dec_b = dec_w + 128;
+    const gnngls::PackedModel m = gnngls::packed_model(in_dim, n_layers);
+    // (the same attention launch shape as the inference forward's, GNNGLS_GAT_HEADS included)
+    const gnngls::AttnStep attn = n_heads == 8 ? gnngls::gat_rows_step(n, forward_switches().gat_heads) : gnngls::gat_heads_rows_step(n, n_heads);
     float *ones = w.COEF + 3 * 128, *zeros = w.COEF + 4 * 128;
     hipError_t e = hipSuccess;
     const float one = 1.f;
@@ -844,9 +828,9 @@ int gnngls_regret_train_forward_heads(const float *feat, const float *params, in
     GNNGLS_TRY(hipMemsetAsync(zeros, 0, 512 * sizeof(float), st));
     const size_t row = (size_t)M * 128;
     { ProfScope ps(GNNGLS_PROF_EMBED, st);
-      GNNGLS_TRY(gnngls::launch_embed(feat, emb_w, emb_b, w.H, M, in_dim, st)); }                       // models.py:66
+      GNNGLS_TRY(gnngls::launch_embed(feat, params + m.emb_w, params + m.emb_b, w.H, M, in_dim, st)); }                       // models.py:66
     for (int l = 0; l < n_layers; ++l) {                                                                // models.py:67-68
-        const LayerParams<const float> p = layer_params(layers + (long)l * kLayerFloats);
+        const LayerParams<const float> p = layer_params(params, m, l);
         const float *h = w.H + row * l;
         float *ft = w.FT + row * l, *g = w.G + row * l, *h1 = w.H1 + row * l, *h3 = w.H3 + row * l;
         float *att = w.ATT + (size_t)M * stat_w * l, *bn = w.BN + (size_t)l * 8 * 128;
@@ -854,19 +838,12 @@ int gnngls_regret_train_forward_heads(const float *feat, const float *params, in
         int nb = 0;
         { ProfScope ps(GNNGLS_PROF_GEMM_FC, st);
           GNNGLS_TRY(gnngls::launch_gemm(gnngls::GEMM_EPI_STORE, h, p.fc_w, ft, M, 128, 128, nullptr, nullptr, nullptr, nullptr, st)); }
-        if (n_heads == 8) {
-          { ProfScope ps(GNNGLS_PROF_GAT_ROWS, st);
-            GNNGLS_TRY(gnngls::launch_gat_rows(ft, p.attn_l, p.attn_r, B, n, w.PART, w.PMS, st)); }
-          { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
-            GNNGLS_TRY(gnngls::launch_gat_combine_train(w.PART, w.PMS, h, M, g, h1, att, st)); }        // models.py:12-15
-        } else {
-          // (H <= 4: slot statistics, gat_combine_train_kernel as for 8 heads; H = 16: per-head statistics and their own merge)
-          { ProfScope ps(GNNGLS_PROF_GAT_ROWS, st);
-            GNNGLS_TRY(gnngls::launch_gat_heads_rows(ft, p.attn_l, p.attn_r, B, n, n_heads, w.PART, w.PMS, w.PMS, st)); }
-          { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
-            if (n_heads == 16) GNNGLS_TRY(gnngls::launch_gat_heads_merge16_train(w.PART, w.PMS, h, M, g, h1, att, st));
-            else GNNGLS_TRY(gnngls::launch_gat_combine_train(w.PART, w.PMS, h, M, g, h1, att, st)); }
-        }
+        { ProfScope ps(GNNGLS_PROF_GAT_ROWS, st);
+          GNNGLS_TRY(launch_attention(attn, ft, p.attn_l, p.attn_r, B, n, w.PART, w.PMS, w.PMS, st)); }
+        // (H <= 8: slot statistics, gat_combine_train_kernel, models.py:12-15; H = 16: per-head statistics and their own merge)
+        { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
+          if (n_heads == 16) GNNGLS_TRY(gnngls::launch_gat_heads_merge16_train(w.PART, w.PMS, h, M, g, h1, att, st));
+          else GNNGLS_TRY(gnngls::launch_gat_combine_train(w.PART, w.PMS, h, M, g, h1, att, st)); }
         { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);                                                   // models.py:27 (train mode)
           GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_SUM_SQ, h1, nullptr, nullptr, M, 128, 0, w.CSP, &nb, st));
           GNNGLS_TRY(gnngls::launch_bn_stats_finalize(w.CSP, nb, M, p.bn1_g, p.bn1_b, bn_eps, bn + 2 * 128, bn + 3 * 128, bn,
@@ -882,7 +859,7 @@ int gnngls_regret_train_forward_heads(const float *feat, const float *params, in
           GNNGLS_TRY(gnngls::launch_affine_cols(h3, bn + 6 * 128, bn + 7 * 128, w.H + row * (l + 1), M, st)); }
     }
     { ProfScope ps(GNNGLS_PROF_DECISION, st);
-      GNNGLS_TRY(gnngls::launch_decision(w.H + row * n_layers, dec_w, dec_b, y_out, M, st)); }          // models.py:69
+      GNNGLS_TRY(gnngls::launch_decision(w.H + row * n_layers, params + m.dec_w, params + m.dec_b, y_out, M, st)); }          // models.py:69
     return GNNGLS_OK;
 }
 
@@ -901,10 +878,9 @@ int gnngls_regret_train_backward_heads(const float *feat, const float *params, c
     const long N = (long)n * (n - 1) / 2, M = (long)B * N;
     const int stat_w = n_heads == 16 ? 32 : 16;
     const TrainWs w = train_layout((uintptr_t)workspace, M, n_layers, stat_w);
-    const float *layers = params + 128L * in_dim + 128;
-    const float *dec_w = layers + (long)n_layers * kLayerFloats;
-    float *g_emb_w = grads, *g_emb_b = grads + 128L * in_dim, *g_layers = g_emb_b + 128;
-    float *g_dec_w = g_layers + (long)n_layers * kLayerFloats, *g_dec_b = g_dec_w + 128;
+    const gnngls::PackedModel m = gnngls::packed_model(in_dim, n_layers);       // the parameters and, same layout, their gradients
+    const float *dec_w = params + m.dec_w;
+    float *g_emb_w = grads + m.emb_w, *g_emb_b = grads + m.emb_b, *g_dec_w = grads + m.dec_w, *g_dec_b = grads + m.dec_b;
     const size_t row = (size_t)M * 128;
     hipError_t e = hipSuccess;
     int nb = 0;
@@ -917,8 +893,8 @@ int gnngls_regret_train_backward_heads(const float *feat, const float *params, c
     { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
       GNNGLS_TRY(gnngls::launch_outer_rows(dy, dec_w, w.DA, M, st)); }
     for (int l = n_layers - 1; l >= 0; --l) {
-        const LayerParams<const float> p = layer_params(layers + (long)l * kLayerFloats);
-        const LayerParams<float> d = layer_params(g_layers + (long)l * kLayerFloats);
+        const LayerParams<const float> p = layer_params(params, m, l);
+        const LayerParams<float> d = layer_params(grads, m, l);
         const float *h = w.H + row * l, *ft = w.FT + row * l, *g = w.G + row * l, *h1 = w.H1 + row * l, *h3 = w.H3 + row * l;
         const float *att = w.ATT + (size_t)M * stat_w * l, *bn = w.BN + (size_t)l * 8 * 128;
         // BatchNorm 2 backward (models.py:35): DA = d(layer output) -> DB = d h3

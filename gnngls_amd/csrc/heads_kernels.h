@@ -1,19 +1,17 @@
 // heads_kernels.h -- internal interface between the attention kernels for head counts other than 8 (heads_kernels.hip) and capi.hip.
-// embed_dim 128: H in {1, 2, 4, 16} heads of F = 128 / H features; n <= heads_max_nodes() for every launcher here.
+// embed_dim 128: H in {1, 2, 4, 16} heads of F = 128 / H features; n <= kMaxNodes (model_policy.h) for every launcher here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace gnngls {
 
-bool heads_supported(int n_heads);        // {1, 2, 4, 8, 16} (8 = the kernels of model_kernels.hip / train_kernels.hip)
-int heads_max_nodes();                    // 257
-size_t gat_heads_rows_lds_bytes(int n, int n_heads);
 size_t gat_heads_bwd_lds_bytes(int n, int n_heads);
 // attention partials of every row: `part` [2][B N][128] by side; statistics into part_ms [2][B N][8 + 8] per 16-column slot
-// (H <= 4) or into hms [2][B N][16 + 16] per head (H = 16, then launch_gat_heads_merge16 before the feed-forward launch)
-hipError_t launch_gat_heads_rows(const float *ft, const float *attn_l, const float *attn_r, int B, int n, int n_heads, float *part,
-                                 float *part_ms, float *hms, hipStream_t st);
+// (H <= 4) or into hms [2][B N][16 + 16] per head (H = 16, then launch_gat_heads_merge16 before the feed-forward launch);
+// waves: gat_heads_rows_step() of the plan
+hipError_t launch_gat_heads_rows(const float *ft, const float *attn_l, const float *attn_r, int B, int n, int n_heads, int waves,
+                                 float *part, float *part_ms, float *hms, hipStream_t st);
 // H = 16: the merged GATConv output into part side 0 (side 1 zero) with neutral statistics in part_ms (inference) ...
 hipError_t launch_gat_heads_merge16(float *part, const float *hms, float *part_ms, long M, hipStream_t st);
 // ... or g, h1 = h + g and att [M][16 + 16] (row max, 1/Z per head) for the training step

@@ -19,16 +19,15 @@
 #include <stdint.h>
 
 #include "heads_kernels.h"
+#include "model_policy.h"
 
 namespace gnngls {
 
 namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kD = 128;
 constexpr float kSlope = 0.2f;                  // GATConv negative_slope default
 constexpr float kLog2e = 1.4426950408889634f;
-constexpr int kMaxNodes = 257;                  // n limit of every kernel here (n - 1 <= 256 sources per row)
 
 __device__ __forceinline__ int pair_rank(int i, int j, int n) {   // i < j, rank in itertools.combinations order
     return i * n - ((i * (i + 1)) >> 1) + (j - i - 1);
@@ -58,17 +57,7 @@ int ew_grid(long M) { return grid_cap((M * 32 + 255) / 256, 256 * 16); }
 // count per layer is that of the 8-head kernel); for F == 8 a 16-column block spans two heads and takes two MFMAs, each with the
 // other head's 8 columns of the B operand zeroed (exact: the zeroed columns add w * 0 = 0).
 // ---------------------------------------------------------------------------------------------
-template <int F>
-struct HeadShape {
-    static constexpr int CW = F == 128 ? 128 : 64;      // columns per workgroup: a head is never split (el / er need all F)
-    static constexpr int HS = CW / F;                    // heads per workgroup: 1, 1, 2, 8
-    static constexpr int HG = kD / CW;                   // workgroups per (instance, row)
-    static constexpr int LDF = CW + 16;                  // LDS row stride (floats) of the ft tile, 16 (mod 64) as gat_rows_kernel
-    static constexpr int UH = F >= 64 ? 1 : 64 / F;      // heads of a 64-column unit: 1, 1, 2, 8
-    static constexpr int UNITS = CW / 64;                // units per 16-destination tile
-    static constexpr int LP = F >= 16 ? F / 16 : 1;      // lanes per (source, head) logit pair, 16 (F = 8: 8) features each
-};
-
+// HeadShape<F>, the carve of a workgroup: model_policy.h
 template <int F>
 __global__ __launch_bounds__(512) void gat_heads_rows_kernel(const float *__restrict__ ft, const float *__restrict__ attn_l,
                                                              const float *__restrict__ attn_r, int n, float *__restrict__ part,
@@ -545,30 +534,14 @@ __global__ __launch_bounds__(256) void colsum_heads16_kernel(const float *__rest
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
-bool heads_supported(int n_heads) { return n_heads == 1 || n_heads == 2 || n_heads == 4 || n_heads == 8 || n_heads == 16; }
-int heads_max_nodes() { return kMaxNodes; }
-
-template <int F>
-static size_t heads_rows_lds(int n) {
-    using S = HeadShape<F>;
-    const size_t ns = (size_t)n - 1;
-    return ns * S::LDF * 4 + 4 * ns * S::HS * 4 + (size_t)S::HS * 4 * 4 + ns * 4 + 16;
-}
+static_assert(HeadShape<128>::UNITS == 2 && HeadShape<64>::UNITS == 1 && HeadShape<32>::UNITS == 1 && HeadShape<8>::UNITS == 1,
+              "gat_heads_rows_units() counts the 64-column units of a workgroup");
 
 template <int F>
 static size_t heads_bwd_lds(int n) {
     using S = BwdShape<F>;
     const size_t ns = (size_t)n - 1;
     return ns * S::HB * 16 + ns * S::LDG * 4 + ns * S::HB * 4 + (size_t)S::WAVES * ns * 4 + ns * 4 + 16;
-}
-
-size_t gat_heads_rows_lds_bytes(int n, int n_heads) {
-    switch (n_heads) {
-    case 1: return heads_rows_lds<128>(n);
-    case 2: return heads_rows_lds<64>(n);
-    case 4: return heads_rows_lds<32>(n);
-    default: return heads_rows_lds<8>(n);
-    }
 }
 
 size_t gat_heads_bwd_lds_bytes(int n, int n_heads) {
@@ -581,35 +554,27 @@ size_t gat_heads_bwd_lds_bytes(int n, int n_heads) {
 }
 
 template <int F>
-static hipError_t launch_rows(const float *ft, const float *attn_l, const float *attn_r, int B, int n, float *part, float *part_ms,
-                              float *hms, hipStream_t st) {
+static hipError_t launch_rows(const float *ft, const float *attn_l, const float *attn_r, int B, int n, int waves, float *part,
+                              float *part_ms, float *hms, hipStream_t st) {
     using S = HeadShape<F>;
     const size_t lds = heads_rows_lds<F>(n);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(gat_heads_rows_kernel<F>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    // units = (16-destination tiles) x (64-column units) over 4..8 waves: the wave count with the fewest idle wave slots (at least
-    // 4: the top-2 pass takes 32 lanes per head of the workgroup)
-    const int units = ((n - 1 + 15) / 16) * S::UNITS;
-    int waves = 4;
-    for (int w = 5; w <= 8; ++w) {
-        const int idle_w = (units + w - 1) / w * w - units, idle_b = (units + waves - 1) / waves * waves - units;
-        if (idle_w < idle_b) waves = w;
-    }
     (void)hipGetLastError();
     hipLaunchKernelGGL(gat_heads_rows_kernel<F>, dim3((unsigned)(B * n * S::HG)), dim3(64 * waves), lds, st, ft, attn_l, attn_r, n,
                        part, part_ms, hms);
     return hipGetLastError();
 }
 
-hipError_t launch_gat_heads_rows(const float *ft, const float *attn_l, const float *attn_r, int B, int n, int n_heads, float *part,
-                                 float *part_ms, float *hms, hipStream_t st) {
-    if (n < 3 || n > kMaxNodes) return hipErrorInvalidValue;
+hipError_t launch_gat_heads_rows(const float *ft, const float *attn_l, const float *attn_r, int B, int n, int n_heads, int waves,
+                                 float *part, float *part_ms, float *hms, hipStream_t st) {
+    if (n < 3 || n > kMaxNodes || waves < 4 || waves > 8) return hipErrorInvalidValue;
     switch (n_heads) {
-    case 1: return launch_rows<128>(ft, attn_l, attn_r, B, n, part, part_ms, hms, st);
-    case 2: return launch_rows<64>(ft, attn_l, attn_r, B, n, part, part_ms, hms, st);
-    case 4: return launch_rows<32>(ft, attn_l, attn_r, B, n, part, part_ms, hms, st);
-    case 16: return launch_rows<8>(ft, attn_l, attn_r, B, n, part, part_ms, hms, st);
+    case 1: return launch_rows<128>(ft, attn_l, attn_r, B, n, waves, part, part_ms, hms, st);
+    case 2: return launch_rows<64>(ft, attn_l, attn_r, B, n, waves, part, part_ms, hms, st);
+    case 4: return launch_rows<32>(ft, attn_l, attn_r, B, n, waves, part, part_ms, hms, st);
+    case 16: return launch_rows<8>(ft, attn_l, attn_r, B, n, waves, part, part_ms, hms, st);
     default: return hipErrorInvalidValue;
     }
 }

@@ -26,6 +26,7 @@
 #include <stdlib.h>
 
 #include "model_kernels.h"
+#include "model_plan.h"
 
 namespace gnngls {
 
@@ -58,10 +59,7 @@ __device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
 // (three instructions per maximum)
 __device__ __forceinline__ float max_f32(float a, float b) { float d; asm("v_max_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
 
-constexpr int kD = 128;        // embed_dim
-constexpr int kEmbedFcMaxIn = 32;     // input features the fused embed + first fc is prepared for (embed_fc_kernel)
-constexpr int kH = 8;          // heads
-constexpr int kF = 16;         // head dim
+// kD, kH, kF, kEmbedFcMaxIn: model_policy.h
 constexpr float kSlope = 0.2f; // GATConv negative_slope default
 
 // ---------------------------------------------------------------------------------------------
@@ -1026,8 +1024,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int FB_M = FB_M_ROWS;                     // rows per workgroup
 constexpr int FB_T = FB_M * 4, FB_W = FB_M / 16;      // threads, wavefronts (16 rows each)
 constexpr bool kFbAlias = FB_M < 128;                // the weight ring in the place of the x tile (staging area of the prologue only)
-constexpr int FB_STAGE = 8 * 3 * 64 * 16;          // bytes of one weight stage: 8 tiles x 3 pieces x 64 lanes x 16 B
-constexpr size_t kFfnPackedBytes = (size_t)(2 * 16 + 4) * FB_STAGE;  // W1p + W2p + the next layer's fc: 884,736 B
+constexpr int FB_STAGE = kFfnStageBytes;            // bytes of one weight stage (kFfnPackedBytes: 2 * 16 + 4 of them per layer)
 
 __device__ __forceinline__ void split_bf16x3(const float (&x)[8], bf16x8 &p0, bf16x8 &p1, bf16x8 &p2) {
 #pragma unroll
@@ -1428,17 +1425,6 @@ static int grid_for(long total, int block, int cap = 256 * 16) {
     return (int)g;
 }
 
-static size_t gat_rows_lds_bytes_hs(int n, int hs) {
-    size_t ns = (size_t)n - 1;
-    return ns * (size_t)(hs * kF + 16) * 4 + 4 * ns * hs * 4 + (size_t)hs * 4 * 4 + ns * 4 + 16;
-}
-// heads per workgroup: all 8 while at least two such workgroups fit a CU, else the head-split form (4).  Measured per
-// launch (profiles/r02_ab_gat_heads.log): TSP200 x 256 11.5 -> 8.5 ms with the split (one -> two workgroups per CU);
-// TSP100 x 1024 5.33 -> 5.69 ms, TSP50 x 2048 1.73 -> 1.82 ms (two+ workgroups already hide the prologue; the split
-// only adds workgroup starts), so it is used where the unsplit tile leaves a CU with a single workgroup.
-static int gat_rows_heads(int n) { return gat_rows_lds_bytes_hs(n, kH) * 2 <= (size_t)160 * 1024 ? kH : 4; }
-size_t gat_rows_lds_bytes(int n) { return gat_rows_lds_bytes_hs(n, gat_rows_heads(n)); }
-
 hipError_t launch_pack_features(const double *D, int B, int n, double scale, double minv, float *feat, hipStream_t st) {
     long total = (long)B * (n * (n - 1) / 2);
     (void)hipGetLastError();
@@ -1453,9 +1439,7 @@ hipError_t launch_unpack_regret(const float *y, int B, int n, double scale, doub
     return hipGetLastError();
 }
 
-size_t embed_fc_bytes() { return ((size_t)(kEmbedFcMaxIn + 1) * kD + 4 * kH) * sizeof(float); }
-int embed_fc_max_in_dim() { return kEmbedFcMaxIn; }
-// A [in_dim,128], b' [128] (and for in_dim == 1 the logit coefficients al | bl | ar | br [8] each) at `image` (embed_fc_bytes() of
+// A [in_dim,128], b' [128] (and for in_dim == 1 the logit coefficients al | bl | ar | br [8] each) at `image` (kEmbedFcBytes of
 // device memory), from the embedding and the first layer's fc and attention weights
 hipError_t launch_embed_fc_prepare(const float *We, const float *be, const float *Wfc, const float *attn_l, const float *attn_r,
                                    int in_dim, void *image, hipStream_t st) {
@@ -1475,11 +1459,11 @@ hipError_t launch_embed_fc(const float *x, const float *W, const float *b, const
 // the first GATConv from the one input feature (in_dim == 1): same partials as launch_gat_rows on ft = x A + b'
 hipError_t launch_gat_rows_rank1(const float *x, const void *image, int B, int n, float *part, float *part_ms, hipStream_t st, bool compact) {
     const float *A = (const float *)image;
-    const int units = ((n - 1 + 63) / 64) * 2;                 // (64 destinations, 4 heads) per wavefront
-    const size_t lds = (size_t)(n - 1) * (2 + 2 * kH) * sizeof(float) + kH * 4 * sizeof(float) + 16;
+    const dim3 grid((unsigned)(B * n)), block(64 * gat_rank1_waves(n));
+    const size_t lds = gat_rank1_lds_bytes(n);
     (void)hipGetLastError();
-    if (compact) hipLaunchKernelGGL(gat_rows_rank1_kernel<true>, dim3((unsigned)(B * n)), dim3(64 * (units < 4 ? 4 : units)), lds, st, x, A, n, part, part_ms);
-    else hipLaunchKernelGGL(gat_rows_rank1_kernel<false>, dim3((unsigned)(B * n)), dim3(64 * (units < 4 ? 4 : units)), lds, st, x, A, n, part, part_ms);
+    if (compact) hipLaunchKernelGGL(gat_rows_rank1_kernel<true>, grid, block, lds, st, x, A, n, part, part_ms);
+    else hipLaunchKernelGGL(gat_rows_rank1_kernel<false>, grid, block, lds, st, x, A, n, part, part_ms);
     return hipGetLastError();
 }
 
@@ -1518,36 +1502,23 @@ hipError_t launch_gemm(int epi, const float *A, const float *W, float *C, long M
 }
 
 template <int HS>
-static hipError_t launch_gat_rows_hs(const float *ft, const float *attn_l, const float *attn_r, int B, int n, float *part,
+static hipError_t launch_gat_rows_hs(const float *ft, const float *attn_l, const float *attn_r, int B, int n, int waves, float *part,
                                      float *part_ms, hipStream_t st) {
     const size_t lds = gat_rows_lds_bytes_hs(n, HS);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(gat_rows_kernel<HS>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     (void)hipGetLastError();
-    // units = (16-destination tiles) x (head quads of the workgroup), spread over 4..8 waves: the wave count with the
-    // fewest idle wave slots; on ties the one that brings the CU closest to 16 resident waves at the LDS-limited
-    // workgroup count
-    const int units = ((n - 1 + 15) / 16) * (HS / 4);
-    const int wgs_per_cu = (int)((size_t)160 * 1024 / lds) > 0 ? (int)((size_t)160 * 1024 / lds) : 1;
-    const int want = 16 / wgs_per_cu > 0 ? 16 / wgs_per_cu : 1;
-    int waves = 4;
-    for (int w = 5; w <= 8; ++w) {
-        const int idle_w = (units + w - 1) / w * w - units, idle_b = (units + waves - 1) / waves * waves - units;
-        const int dw = w > want ? w - want : want - w, db = waves > want ? waves - want : want - waves;
-        if (idle_w < idle_b || (idle_w == idle_b && dw < db)) waves = w;
-    }
     hipLaunchKernelGGL(gat_rows_kernel<HS>, dim3((unsigned)(B * n * (kH / HS))), dim3(64 * waves), lds, st, ft, attn_l, attn_r,
                        n, part, part_ms);
     return hipGetLastError();
 }
 
-hipError_t launch_gat_rows(const float *ft, const float *attn_l, const float *attn_r, int B, int n, float *part,
-                           float *part_ms, hipStream_t st) {
-    static const char *force = getenv("GNNGLS_GAT_HEADS");      // experiments: 8 or 4
-    const int hs = force ? atoi(force) : gat_rows_heads(n);
-    return hs == 4 ? launch_gat_rows_hs<4>(ft, attn_l, attn_r, B, n, part, part_ms, st)
-                   : launch_gat_rows_hs<kH>(ft, attn_l, attn_r, B, n, part, part_ms, st);
+// heads_per_wg (8 or 4) and waves: gat_rows_step() of the plan
+hipError_t launch_gat_rows(const float *ft, const float *attn_l, const float *attn_r, int B, int n, int heads_per_wg, int waves,
+                           float *part, float *part_ms, hipStream_t st) {
+    return heads_per_wg == 4 ? launch_gat_rows_hs<4>(ft, attn_l, attn_r, B, n, waves, part, part_ms, st)
+                             : launch_gat_rows_hs<kH>(ft, attn_l, attn_r, B, n, waves, part, part_ms, st);
 }
 
 template <int MODE>
@@ -1565,9 +1536,7 @@ static hipError_t launch_ffn_mode(const float *part, const float *part_ms, const
     return hipGetLastError();
 }
 
-size_t ffn_packed_bytes() { return kFfnPackedBytes; }
-
-// One layer's feed-forward weights (and, if given, the NEXT layer's fc) split into bf16 pieces in fragment order: ffn_packed_bytes()
+// One layer's feed-forward weights (and, if given, the NEXT layer's fc) split into bf16 pieces in fragment order: kFfnPackedBytes
 // of device memory.  The image depends on the weights only -- gnngls_regret_prepare builds it once per weight image for all layers.
 hipError_t launch_ffn_pack(const float *W1, const float *W2, const float *fc_next, void *packed, hipStream_t st) {
     unsigned char *pk = (unsigned char *)packed, *pk_fc = pk + (size_t)2 * 16 * FB_STAGE;
@@ -1577,14 +1546,12 @@ hipError_t launch_ffn_pack(const float *W1, const float *W2, const float *fc_nex
     return hipGetLastError();
 }
 
-// packed != nullptr (a layer image made by launch_ffn_pack): the bf16x3 kernel; else the fp32 kernel.  With the bf16x3 kernel and
-// has_fc_next the NEXT layer's ft = fc_next(hout) [M,128] is written to ft_out by the same launch (models.py:23 of layer l + 1)
-hipError_t launch_ffn_fused(const float *part, const float *part_ms, const float *hin, const float *bn1_s,
-                            const float *bn1_b, const float *W1, const float *b1, const float *W2, const float *b2,
-                            const float *bn2_s, const float *bn2_b, float *hout, long M, const void *packed, bool has_fc_next,
-                            float *ft_out, hipStream_t st, const float *dec_w, const float *dec_b, float *y_out,
-                            const float *lr_img, const float *emb_w, const float *emb_b) {
-    if (packed) {
+// form.bf16x3 (a.packed: a layer image made by launch_ffn_pack): the bf16x3 kernel; else the fp32 kernel.  With the bf16x3 kernel
+// and form.writes_next_ft the NEXT layer's ft = fc_next(hout) [M,128] is written to ft_out by the same launch (models.py:23 of layer
+// l + 1); form.decision: y_out[m] = hout[m,:] . dec_w + dec_b[0], hout not stored; form.rank1_input: `part` = the compact partials of
+// gat_rows_rank1_kernel<true>, `hin` = the [M] input features, lr_img = the embed-fc image
+hipError_t launch_ffn_fused(const FfnFused &a, const FfnStep &form, hipStream_t st) {
+    if (form.bf16x3) {
         const size_t xt = (size_t)FB_M * LDX * sizeof(float), ring = (size_t)3 * FB_STAGE;
         const size_t lds = (kFbAlias ? (xt > ring ? xt : ring) : xt + ring) + 896 * sizeof(float);
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ffn_fused_bf16x3_kernel<false>),
@@ -1593,19 +1560,20 @@ hipError_t launch_ffn_fused(const float *part, const float *part_ms, const float
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(ffn_fused_bf16x3_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         (void)hipGetLastError();
-        const unsigned char *pk = (const unsigned char *)packed, *pk_fc = pk + (size_t)2 * 16 * FB_STAGE;
-        if (lr_img)        // (`part` = the compact partials of gat_rows_rank1_kernel<true>, `hin` = the [M] input features)
-            hipLaunchKernelGGL(ffn_fused_bf16x3_kernel<true>, dim3((unsigned)((M + FB_M - 1) / FB_M)), dim3(FB_T), lds, st, part, part_ms, hin,
-                               bn1_s, bn1_b, pk, b1, b2, bn2_s, bn2_b, hout, M, has_fc_next ? pk_fc : nullptr, ft_out,
-                               dec_w, dec_b, y_out, lr_img, emb_w, emb_b);
+        const unsigned char *pk = (const unsigned char *)a.packed, *pk_fc = form.writes_next_ft ? pk + (size_t)2 * 16 * FB_STAGE : nullptr;
+        const float *dec_w = form.decision ? a.dec_w : nullptr, *dec_b = form.decision ? a.dec_b : nullptr;
+        float *y_out = form.decision ? a.y_out : nullptr;
+        const dim3 grid((unsigned)((a.M + FB_M - 1) / FB_M));
+        if (form.rank1_input)
+            hipLaunchKernelGGL(ffn_fused_bf16x3_kernel<true>, grid, dim3(FB_T), lds, st, a.part, a.part_ms, a.hin, a.bn1_s, a.bn1_b, pk, a.b1,
+                               a.b2, a.bn2_s, a.bn2_b, a.hout, a.M, pk_fc, a.ft_out, dec_w, dec_b, y_out, a.lr_img, a.emb_w, a.emb_b);
         else
-            hipLaunchKernelGGL(ffn_fused_bf16x3_kernel<false>, dim3((unsigned)((M + FB_M - 1) / FB_M)), dim3(FB_T), lds, st, part, part_ms, hin,
-                               bn1_s, bn1_b, pk, b1, b2, bn2_s, bn2_b, hout, M, has_fc_next ? pk_fc : nullptr, ft_out,
-                               dec_w, dec_b, y_out, nullptr, nullptr, nullptr);
+            hipLaunchKernelGGL(ffn_fused_bf16x3_kernel<false>, grid, dim3(FB_T), lds, st, a.part, a.part_ms, a.hin, a.bn1_s, a.bn1_b, pk, a.b1,
+                               a.b2, a.bn2_s, a.bn2_b, a.hout, a.M, pk_fc, a.ft_out, dec_w, dec_b, y_out, nullptr, nullptr, nullptr);
         return hipGetLastError();
     }
-    return launch_ffn_mode<FFN_INFER>(part, part_ms, hin, bn1_s, bn1_b, W1, b1, W2, b2, bn2_s, bn2_b, hout, M, nullptr,
-                                      nullptr, st);
+    return launch_ffn_mode<FFN_INFER>(a.part, a.part_ms, a.hin, a.bn1_s, a.bn1_b, a.W1, a.b1, a.W2, a.b2, a.bn2_s, a.bn2_b, a.hout, a.M,
+                                      nullptr, nullptr, st);
 }
 
 // training forward: h3 = x + W2*ReLU(W1*x + b1) + b2 with x = h1*bn1_s + bn1_b, hidden activations kept in `hidden`
