@@ -28,7 +28,7 @@ HEADERS = {
     "gls_plan.cpp": ["gls_plan.h", "gls_policy.h"],
     "model_kernels.hip": ["model_kernels.h", "model_plan.h", "model_policy.h"],
     "model_plan.cpp": ["model_plan.h", "model_policy.h", os.path.join("..", "..", "include", "gnngls_hip.h")],
-    "train_kernels.hip": ["train_kernels.h", "model_kernels.h"],
+    "train_kernels.hip": ["train_kernels.h", "model_policy.h"],
     "heads_kernels.hip": ["heads_kernels.h", "model_policy.h"],
     "labels_kernels.hip": ["labels_kernels.h", "gls_kernels.h", "gls_plan.h", "gls_policy.h"],
     "constructors_kernels.hip": ["constructors_kernels.h", "gls_common.h", "gls_policy.h"],

@@ -487,7 +487,6 @@ int gnngls_regret_labels(const double *D, int B, int n, const int32_t *base_tour
 // GNN forward
 // ---------------------------------------------------------------------------------------------
 namespace {
-using gnngls::kModelLdsPerCU;
 // the parameters of one layer inside the packed weights (and, with T = float, of their gradients)
 template <typename T>
 struct LayerParams { T *fc_w, *attn_l, *attn_r, *bn1_g, *bn1_b, *w1, *b1, *w2, *b2, *bn2_g, *bn2_b; };
@@ -557,7 +556,7 @@ int gnngls_regret_prepare(const float *weights, int in_dim, int n_layers, void *
 }  // extern "C"
 
 namespace {
-// the attention of one layer as the plan (or, for the training step, gat_rows_step / gat_heads_rows_step) shaped it
+// the attention of one layer as the plan (of the forward or of the training step) shaped it
 hipError_t launch_attention(const gnngls::AttnStep &a, const float *ft, const float *attn_l, const float *attn_r, int B, int n,
                             float *part, float *part_ms, float *hms, hipStream_t st) {
     if (a.form == gnngls::ATTN_K1) return gnngls::launch_gat_rows(ft, attn_l, attn_r, B, n, a.heads_per_wg, a.waves, part, part_ms, st);
@@ -712,79 +711,36 @@ int gnngls_unpack_regret(const float *y, int B, int n, double scale, double min_
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-// Device workspace of one training step for M = B*N rows and L layers.  The first group is written by the forward and
-// read by the backward (it must survive between the two calls); the second group is scratch.
-struct TrainWs {
-    float *H;        // [(L+1)][M][128]  layer inputs (H[0] = embedding) and the final hidden state
-    float *FT;       // [L][M][128]      fc(h)
-    float *G;        // [L][M][128]      GATConv output
-    float *H1;       // [L][M][128]      h + GATConv(h)
-    float *H3;       // [L][M][128]      x + MLP(x), x = BN1(h1)
-    float *HID;      // [L][M][512]      ReLU(W1 x + b1); overwritten by its gradient in the backward
-    float *ATT;      // [L][M][16]       softmax statistics (row max, 1/Z) per head (16 heads: [L][M][32])
-    float *BN;       // [L][8][128]      mean1 invstd1 scale1 shift1 mean2 invstd2 scale2 shift2
-    float *PART;     // [2][M][128]      attention partials (forward) / P partials (backward)
-    float *PMS;      // [2][M][16]       (16 heads: [2][M][32])
-    float *DA, *DB;  // [M][128]         gradient ping-pong
-    float *X2;       // [M][128]         BN1 output recomputed in the backward
-    float *DFT;      // [M][128]
-    float *DLR;      // [2][M][8]        d el, d er (16 heads: [2][M][16])
-    float *WT;       // [2][512*128]     W2^T, W1^T of the layer being differentiated
-    float *COEF;     // [3][128] + ones[128] + zeros[512]   BatchNorm backward coefficients, constants
-    double *CSP;     // column-sum partials
-    float *TNP;      // weight-gradient partial tiles
-    size_t bytes;
-};
-
-// stat_w: softmax statistics per node, 16 (one shift and one sum per 16-column slot, H <= 8) or 32 (16 heads)
-TrainWs train_layout(uintptr_t base, long M, int L, int stat_w = 16) {
-    TrainWs w;
-    uintptr_t p = (base + 255) & ~(uintptr_t)255;
-    auto take = [&](size_t bytes) { uintptr_t q = p; p = (p + bytes + 255) & ~(uintptr_t)255; return q; };
-    const size_t row = (size_t)M * 128 * sizeof(float);
-    w.H = (float *)take(row * (L + 1));
-    w.FT = (float *)take(row * L);
-    w.G = (float *)take(row * L);
-    w.H1 = (float *)take(row * L);
-    w.H3 = (float *)take(row * L);
-    w.HID = (float *)take(4 * row * L);
-    w.ATT = (float *)take((size_t)M * stat_w * sizeof(float) * L);
-    w.BN = (float *)take((size_t)L * 8 * 128 * sizeof(float));
-    w.PART = (float *)take(2 * row);
-    w.PMS = (float *)take((size_t)2 * M * stat_w * sizeof(float));
-    w.DA = (float *)take(row);
-    w.DB = (float *)take(row);
-    w.X2 = (float *)take(row);
-    w.DFT = (float *)take(row);
-    w.DLR = (float *)take((size_t)2 * M * (stat_w / 2) * sizeof(float));
-    w.WT = (float *)take((size_t)2 * 512 * 128 * sizeof(float));
-    w.COEF = (float *)take((4 * 128 + 512) * sizeof(float));
-    w.CSP = (double *)take((size_t)gnngls::kColsumMaxBlocks * 2 * 512 * sizeof(double));
-    w.TNP = (float *)take((size_t)gnngls::gemm_tn_chunks(M) * (128 * 512 + 512) * sizeof(float));
-    w.bytes = (size_t)(p - base);
-    return w;
+// Both halves of the step: makes the request, takes the plan (model_plan.cpp: the refusals, the workspace layout, the attention
+// forms of both ways) and prints its refusal.  io: y_out / grads.
+int train_begin(const char *what, const void *feat, const void *params, const void *io, const void *workspace, int B, int n, int in_dim,
+                int n_layers, int n_heads, int64_t workspace_bytes, gnngls::TrainPlan &plan) {
+    plan = gnngls::train_plan({n, B, in_dim, n_layers, n_heads, feat && params && io && workspace, workspace_bytes,
+                               forward_switches().gat_heads});
+    switch (plan.why) {
+    case gnngls::TRAIN_OK: break;
+    case gnngls::TRAIN_BAD_HEADS: return heads_fail(what, n_heads);
+    case gnngls::TRAIN_BAD_ARG: return fail(plan.status, "%s: bad argument", what);
+    case gnngls::TRAIN_BWD_NODES:
+        return fail(plan.status, "%s: n=%d exceeds the attention-backward tile limit (n <= %d)", what, n, (int)plan.number);
+    case gnngls::TRAIN_WORKSPACE_SMALL:
+        return fail(plan.status, "%s: workspace too small (%lld B, need %lld B)", what, (long long)workspace_bytes, (long long)plan.number);
+    }
+    return GNNGLS_OK;
 }
 
-int train_check(const char *what, const void *feat, const void *params, const void *io, const void *workspace, int B, int n,
-                int in_dim, int n_layers, int64_t workspace_bytes, int n_heads = 8) {
-    if (!gnngls::heads_supported(n_heads)) return heads_fail(what, n_heads);
-    if (!feat || !params || !io || !workspace || B < 1 || n < 3 || in_dim < 1 || n_layers < 0)
-        return fail(GNNGLS_ERR_ARG, "%s: bad argument", what);
-    if (n > gnngls::gat_bwd_max_nodes())
-        return fail(GNNGLS_ERR_UNSUPPORTED, "%s: n=%d exceeds the attention-backward tile limit (n <= %d)", what, n,
-                    gnngls::gat_bwd_max_nodes());
-    if (n_heads == 8 && (gnngls::gat_rows_lds_bytes(n) > kModelLdsPerCU || gnngls::gat_bwd_lds_bytes(n) > kModelLdsPerCU))
-        return fail(GNNGLS_ERR_UNSUPPORTED, "%s: n=%d needs %zu B of LDS per row tile (> 160 KiB)", what, n,
-                    gnngls::gat_bwd_lds_bytes(n));
-    if (n_heads != 8 && (n > gnngls::kMaxNodes || gnngls::gat_heads_rows_lds_bytes(n, n_heads) > kModelLdsPerCU ||
-                         gnngls::gat_heads_bwd_lds_bytes(n, n_heads) > kModelLdsPerCU))
-        return fail(GNNGLS_ERR_UNSUPPORTED, "%s: n=%d exceeds the %d-head attention tile limit (n <= %d)", what, n, n_heads,
-                    gnngls::kMaxNodes);
-    const int64_t need = gnngls_regret_train_workspace_bytes_heads(B, n, n_layers, n_heads);
-    if (workspace_bytes < need)
-        return fail(GNNGLS_ERR_ARG, "%s: workspace too small (%lld B, need %lld B)", what, (long long)workspace_bytes,
-                    (long long)need);
-    return GNNGLS_OK;
+// the attention backward of one layer as the plan shaped it ...
+hipError_t launch_attention_bwd(const gnngls::AttnBwdStep &a, const float *ft, const float *dout, const float *gout, const float *att,
+                                const float *attn_l, const float *attn_r, int B, int n, float *P, float *dlr, hipStream_t st) {
+    if (a.form == gnngls::ATTN_K1) return gnngls::launch_gat_bwd_rows(ft, dout, gout, att, attn_l, attn_r, B, n, a.tiles, a.lds, P, dlr, st);
+    return gnngls::launch_gat_heads_bwd_rows(ft, dout, gout, att, attn_l, attn_r, B, n, gnngls::kD / a.F, a.lds, P, dlr, st);
+}
+
+// ... and its combine: dft = P + del * attn_l + der * attn_r, d el / d er per slot or (16 heads) per head
+hipError_t launch_attention_bwd_combine(gnngls::CombineForm form, const float *P, const float *dlr, const float *attn_l, const float *attn_r,
+                                        long M, float *dft, float *dl, float *dr, hipStream_t st) {
+    if (form == gnngls::COMBINE_HEADS16) return gnngls::launch_gat_heads_bwd_combine16(P, dlr, attn_l, attn_r, M, dft, dl, dr, st);
+    return gnngls::launch_gat_bwd_combine(P, dlr, attn_l, attn_r, M, dft, dl, dr, st);
 }
 
 }  // namespace
@@ -794,10 +750,7 @@ extern "C" {
 int64_t gnngls_regret_train_workspace_bytes(int B, int n, int n_layers) { return gnngls_regret_train_workspace_bytes_heads(B, n, n_layers, 8); }
 
 int64_t gnngls_regret_train_workspace_bytes_heads(int B, int n, int n_layers, int n_heads) {
-    if (!gnngls::heads_supported(n_heads)) return 0;
-    if (B < 1 || n < 2 || n > 65535 || n_layers < 0 || n_layers > 4096) return 0;
-    const long M = (long)B * ((long)n * (n - 1) / 2);
-    return (int64_t)train_layout(0, M, n_layers, n_heads == 16 ? 32 : 16).bytes + 256;
+    return gnngls::train_workspace_bytes(B, n, n_layers, n_heads);
 }
 
 int gnngls_regret_train_forward(const float *feat, const float *params, int B, int n, int in_dim, int n_layers, float bn_eps,
@@ -809,57 +762,59 @@ int gnngls_regret_train_forward(const float *feat, const float *params, int B, i
 int gnngls_regret_train_forward_heads(const float *feat, const float *params, int B, int n, int in_dim, int n_layers, int n_heads,
                                       float bn_eps, float *y_out, float *bn_batch_stats, void *workspace, int64_t workspace_bytes,
                                       void *stream) {
-    int rc = train_check("regret_train_forward", feat, params, y_out, workspace, B, n, in_dim, n_layers, workspace_bytes, n_heads);
+    gnngls::TrainPlan plan;
+    int rc = train_begin("regret_train_forward", feat, params, y_out, workspace, B, n, in_dim, n_layers, n_heads, workspace_bytes, plan);
     if (rc != GNNGLS_OK) return rc;
     if (!bn_batch_stats && n_layers > 0) return fail(GNNGLS_ERR_ARG, "regret_train_forward: bn_batch_stats is NULL");
     hipStream_t st = (hipStream_t)stream;
-    const long N = (long)n * (n - 1) / 2, M = (long)B * N;
-    const int stat_w = n_heads == 16 ? 32 : 16;
-    const TrainWs w = train_layout((uintptr_t)workspace, M, n_layers, stat_w);
+    const gnngls::TrainLayout &w = plan.ws;
+    const long M = w.M;
+    unsigned char *base = align256(workspace);
+    auto at = [base](size_t offset) { return (float *)(base + offset); };
     const gnngls::PackedModel m = gnngls::packed_model(in_dim, n_layers);
-    // (the same attention launch shape as the inference forward's, GNNGLS_GAT_HEADS included)
-    const gnngls::AttnStep attn = n_heads == 8 ? gnngls::gat_rows_step(n, forward_switches().gat_heads) : gnngls::gat_heads_rows_step(n, n_heads);
-    float *ones = w.COEF + 3 * 128, *zeros = w.COEF + 4 * 128;
+    float *part = at(w.PART), *pms = at(w.PMS), *ones = at(w.ONES), *zeros = at(w.ZEROS);
+    double *csp = (double *)(base + w.CSP);
     hipError_t e = hipSuccess;
     const float one = 1.f;
     uint32_t one_bits;
     memcpy(&one_bits, &one, 4);
     GNNGLS_TRY(hipMemsetD32Async((hipDeviceptr_t)ones, (int)one_bits, 128, st));
     GNNGLS_TRY(hipMemsetAsync(zeros, 0, 512 * sizeof(float), st));
-    const size_t row = (size_t)M * 128;
     { ProfScope ps(GNNGLS_PROF_EMBED, st);
-      GNNGLS_TRY(gnngls::launch_embed(feat, params + m.emb_w, params + m.emb_b, w.H, M, in_dim, st)); }                       // models.py:66
+      GNNGLS_TRY(gnngls::launch_embed(feat, params + m.emb_w, params + m.emb_b, at(w.h(0)), M, in_dim, st)); }                 // models.py:66
     for (int l = 0; l < n_layers; ++l) {                                                                // models.py:67-68
         const LayerParams<const float> p = layer_params(params, m, l);
-        const float *h = w.H + row * l;
-        float *ft = w.FT + row * l, *g = w.G + row * l, *h1 = w.H1 + row * l, *h3 = w.H3 + row * l;
-        float *att = w.ATT + (size_t)M * stat_w * l, *bn = w.BN + (size_t)l * 8 * 128;
-        float *stats = bn_batch_stats + (size_t)l * 4 * 128;
+        const float *h = at(w.h(l));
+        float *ft = at(w.ft(l)), *g = at(w.g(l)), *h1 = at(w.h1(l)), *h3 = at(w.h3(l)), *att = at(w.att(l));
+        float *scale1 = at(w.bn(l, gnngls::BN_SCALE1)), *shift1 = at(w.bn(l, gnngls::BN_SHIFT1));
+        float *scale2 = at(w.bn(l, gnngls::BN_SCALE2)), *shift2 = at(w.bn(l, gnngls::BN_SHIFT2));
         int nb = 0;
         { ProfScope ps(GNNGLS_PROF_GEMM_FC, st);
           GNNGLS_TRY(gnngls::launch_gemm(gnngls::GEMM_EPI_STORE, h, p.fc_w, ft, M, 128, 128, nullptr, nullptr, nullptr, nullptr, st)); }
+        // (16 heads: the per-head statistics of the forward kernel go where the slot statistics go otherwise, into the widened PMS)
         { ProfScope ps(GNNGLS_PROF_GAT_ROWS, st);
-          GNNGLS_TRY(launch_attention(attn, ft, p.attn_l, p.attn_r, B, n, w.PART, w.PMS, w.PMS, st)); }
+          GNNGLS_TRY(launch_attention(plan.attn, ft, p.attn_l, p.attn_r, B, n, part, pms, pms, st)); }
         // (H <= 8: slot statistics, gat_combine_train_kernel, models.py:12-15; H = 16: per-head statistics and their own merge)
         { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
-          if (n_heads == 16) GNNGLS_TRY(gnngls::launch_gat_heads_merge16_train(w.PART, w.PMS, h, M, g, h1, att, st));
-          else GNNGLS_TRY(gnngls::launch_gat_combine_train(w.PART, w.PMS, h, M, g, h1, att, st)); }
+          if (plan.combine == gnngls::COMBINE_HEADS16) GNNGLS_TRY(gnngls::launch_gat_heads_merge16_train(part, pms, h, M, g, h1, att, st));
+          else GNNGLS_TRY(gnngls::launch_gat_combine_train(part, pms, h, M, g, h1, att, st)); }
         { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);                                                   // models.py:27 (train mode)
-          GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_SUM_SQ, h1, nullptr, nullptr, M, 128, 0, w.CSP, &nb, st));
-          GNNGLS_TRY(gnngls::launch_bn_stats_finalize(w.CSP, nb, M, p.bn1_g, p.bn1_b, bn_eps, bn + 2 * 128, bn + 3 * 128, bn,
-                                                      bn + 128, stats, stats + 128, st)); }
+          GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_SUM_SQ, h1, nullptr, nullptr, M, 128, 0, csp, &nb, st));
+          GNNGLS_TRY(gnngls::launch_bn_stats_finalize(csp, nb, M, p.bn1_g, p.bn1_b, bn_eps, scale1, shift1, at(w.bn(l, gnngls::BN_MEAN1)),
+                                                      at(w.bn(l, gnngls::BN_INVSTD1)), bn_batch_stats + gnngls::batch_stat(l, gnngls::STAT_MEAN1),
+                                                      bn_batch_stats + gnngls::batch_stat(l, gnngls::STAT_VAR1), st)); }
         { ProfScope ps(GNNGLS_PROF_FFN_FUSED, st);                                                      // models.py:28-33
-          GNNGLS_TRY(gnngls::launch_ffn_fused_train(h1, bn + 2 * 128, bn + 3 * 128, p.w1, p.b1, p.w2, p.b2, ones, zeros, h3,
-                                                    w.HID + 4 * row * l, M, st)); }
+          GNNGLS_TRY(gnngls::launch_ffn_fused_train(h1, scale1, shift1, p.w1, p.b1, p.w2, p.b2, ones, zeros, h3, at(w.hid(l)), M, st)); }
         { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);                                                   // models.py:35 (train mode)
-          GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_SUM_SQ, h3, nullptr, nullptr, M, 128, 0, w.CSP, &nb, st));
-          GNNGLS_TRY(gnngls::launch_bn_stats_finalize(w.CSP, nb, M, p.bn2_g, p.bn2_b, bn_eps, bn + 6 * 128, bn + 7 * 128,
-                                                      bn + 4 * 128, bn + 5 * 128, stats + 256, stats + 384, st)); }
+          GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_SUM_SQ, h3, nullptr, nullptr, M, 128, 0, csp, &nb, st));
+          GNNGLS_TRY(gnngls::launch_bn_stats_finalize(csp, nb, M, p.bn2_g, p.bn2_b, bn_eps, scale2, shift2, at(w.bn(l, gnngls::BN_MEAN2)),
+                                                      at(w.bn(l, gnngls::BN_INVSTD2)), bn_batch_stats + gnngls::batch_stat(l, gnngls::STAT_MEAN2),
+                                                      bn_batch_stats + gnngls::batch_stat(l, gnngls::STAT_VAR2), st)); }
         { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
-          GNNGLS_TRY(gnngls::launch_affine_cols(h3, bn + 6 * 128, bn + 7 * 128, w.H + row * (l + 1), M, st)); }
+          GNNGLS_TRY(gnngls::launch_affine_cols(h3, scale2, shift2, at(w.h(l + 1)), M, st)); }
     }
     { ProfScope ps(GNNGLS_PROF_DECISION, st);
-      GNNGLS_TRY(gnngls::launch_decision(w.H + row * n_layers, params + m.dec_w, params + m.dec_b, y_out, M, st)); }          // models.py:69
+      GNNGLS_TRY(gnngls::launch_decision(at(w.h(n_layers)), params + m.dec_w, params + m.dec_b, y_out, M, st)); }             // models.py:69
     return GNNGLS_OK;
 }
 
@@ -871,85 +826,82 @@ int gnngls_regret_train_backward(const float *feat, const float *params, const f
 int gnngls_regret_train_backward_heads(const float *feat, const float *params, const float *dy, int B, int n, int in_dim,
                                        int n_layers, int n_heads, float *grads, void *workspace, int64_t workspace_bytes,
                                        void *stream) {
-    int rc = train_check("regret_train_backward", feat, params, grads, workspace, B, n, in_dim, n_layers, workspace_bytes, n_heads);
+    gnngls::TrainPlan plan;
+    int rc = train_begin("regret_train_backward", feat, params, grads, workspace, B, n, in_dim, n_layers, n_heads, workspace_bytes, plan);
     if (rc != GNNGLS_OK) return rc;
     if (!dy) return fail(GNNGLS_ERR_ARG, "regret_train_backward: dy is NULL");
     hipStream_t st = (hipStream_t)stream;
-    const long N = (long)n * (n - 1) / 2, M = (long)B * N;
-    const int stat_w = n_heads == 16 ? 32 : 16;
-    const TrainWs w = train_layout((uintptr_t)workspace, M, n_layers, stat_w);
+    const gnngls::TrainLayout &w = plan.ws;
+    const long M = w.M;
+    unsigned char *base = align256(workspace);
+    auto at = [base](size_t offset) { return (float *)(base + offset); };
     const gnngls::PackedModel m = gnngls::packed_model(in_dim, n_layers);       // the parameters and, same layout, their gradients
     const float *dec_w = params + m.dec_w;
     float *g_emb_w = grads + m.emb_w, *g_emb_b = grads + m.emb_b, *g_dec_w = grads + m.dec_w, *g_dec_b = grads + m.dec_b;
-    const size_t row = (size_t)M * 128;
+    float *part = at(w.PART), *pms = at(w.PMS), *da = at(w.DA), *db = at(w.DB), *x2 = at(w.X2), *dft = at(w.DFT), *dl = at(w.DL), *dr = at(w.DR);
+    float *w2t = at(w.W2T), *w1t = at(w.W1T), *coef = at(w.COEF), *tnp = at(w.TNP);
+    double *csp = (double *)(base + w.CSP);
     hipError_t e = hipSuccess;
     int nb = 0;
     GNNGLS_TRY(hipMemsetAsync(g_dec_b + 1, 0, 3 * sizeof(float), st));                                   // pad
     // decision layer (models.py:69): y = h.w + b
     { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);
-      GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_ROWSCALE, w.H + row * n_layers, dy, nullptr, M, 128, 1, w.CSP, &nb, st));
-      GNNGLS_TRY(gnngls::launch_colsum_store(w.CSP, nb, 128, 1, g_dec_w, nullptr, st));
+      GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_ROWSCALE, at(w.h(n_layers)), dy, nullptr, M, 128, 1, csp, &nb, st));
+      GNNGLS_TRY(gnngls::launch_colsum_store(csp, nb, 128, 1, g_dec_w, nullptr, st));
       GNNGLS_TRY(gnngls::launch_sum_vector(dy, M, g_dec_b, st)); }
     { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
-      GNNGLS_TRY(gnngls::launch_outer_rows(dy, dec_w, w.DA, M, st)); }
+      GNNGLS_TRY(gnngls::launch_outer_rows(dy, dec_w, da, M, st)); }
     for (int l = n_layers - 1; l >= 0; --l) {
         const LayerParams<const float> p = layer_params(params, m, l);
         const LayerParams<float> d = layer_params(grads, m, l);
-        const float *h = w.H + row * l, *ft = w.FT + row * l, *g = w.G + row * l, *h1 = w.H1 + row * l, *h3 = w.H3 + row * l;
-        const float *att = w.ATT + (size_t)M * stat_w * l, *bn = w.BN + (size_t)l * 8 * 128;
+        const float *h = at(w.h(l)), *ft = at(w.ft(l)), *g = at(w.g(l)), *h1 = at(w.h1(l)), *h3 = at(w.h3(l)), *att = at(w.att(l));
+        const float *mean1 = at(w.bn(l, gnngls::BN_MEAN1)), *invstd1 = at(w.bn(l, gnngls::BN_INVSTD1));
+        const float *mean2 = at(w.bn(l, gnngls::BN_MEAN2)), *invstd2 = at(w.bn(l, gnngls::BN_INVSTD2));
         // BatchNorm 2 backward (models.py:35): DA = d(layer output) -> DB = d h3
         { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);
-          GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_SUM_PROD, w.DA, h3, nullptr, M, 128, 0, w.CSP, &nb, st));
-          GNNGLS_TRY(gnngls::launch_bn_bwd_finalize(w.CSP, nb, M, p.bn2_g, bn + 4 * 128, bn + 5 * 128, d.bn2_g, d.bn2_b, w.COEF, st)); }
+          GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_SUM_PROD, da, h3, nullptr, M, 128, 0, csp, &nb, st));
+          GNNGLS_TRY(gnngls::launch_bn_bwd_finalize(csp, nb, M, p.bn2_g, mean2, invstd2, d.bn2_g, d.bn2_b, coef, st)); }
         { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
           // d h3 = BatchNorm-2 backward of DA, and x = BN1(h1) recomputed, in one elementwise pass
-          GNNGLS_TRY(gnngls::launch_bn_bwd_apply_and_affine(w.DA, h3, bn + 4 * 128, w.COEF, w.DB, h1, bn + 2 * 128, bn + 3 * 128,
-                                                            w.X2, M, st));
-          GNNGLS_TRY(gnngls::launch_transpose_pair(p.w2, p.w1, w.WT, w.WT + 512 * 128, st)); }              // W2^T, W1^T
+          GNNGLS_TRY(gnngls::launch_bn_bwd_apply_and_affine(da, h3, mean2, coef, db, h1, at(w.bn(l, gnngls::BN_SCALE1)),
+                                                            at(w.bn(l, gnngls::BN_SHIFT1)), x2, M, st));
+          GNNGLS_TRY(gnngls::launch_transpose_pair(p.w2, p.w1, w2t, w1t, st)); }                             // W2^T, W1^T
         // feed-forward block backward (models.py:28-33): h3 = x + W2 relu(W1 x + b1) + b2
-        float *hid = w.HID + 4 * row * l;                    // saved ReLU(W1 x + b1)
+        float *hid = at(w.hid(l));                           // saved ReLU(W1 x + b1)
         { ProfScope ps(GNNGLS_PROF_TRAIN_GEMM_TN, st);
-          GNNGLS_TRY(gnngls::launch_gemm_tn(w.DB, hid, M, 128, 512, w.TNP, d.w2, d.b2, st)); }   // d W2 and d b2 = colsum(d h3)
+          GNNGLS_TRY(gnngls::launch_gemm_tn(db, hid, M, 128, 512, tnp, d.w2, d.b2, st)); }       // d W2 and d b2 = colsum(d h3)
         { ProfScope ps(GNNGLS_PROF_TRAIN_GEMM_BWD, st);      // d x = ((d h3 * W2) . [relu > 0]) * W1 + d h3; hid <- d pre
-          GNNGLS_TRY(gnngls::launch_ffn_fused_bwd(w.DB, w.WT, w.WT + 512 * 128, w.COEF + 3 * 128, w.COEF + 4 * 128, w.DA, hid, M, st)); }
+          GNNGLS_TRY(gnngls::launch_ffn_fused_bwd(db, w2t, w1t, at(w.ONES), at(w.ZEROS), da, hid, M, st)); }
         { ProfScope ps(GNNGLS_PROF_TRAIN_GEMM_TN, st);
-          GNNGLS_TRY(gnngls::launch_gemm_tn(hid, w.X2, M, 512, 128, w.TNP, d.w1, d.b1, st)); }   // d W1 and d b1 = colsum(d pre)
+          GNNGLS_TRY(gnngls::launch_gemm_tn(hid, x2, M, 512, 128, tnp, d.w1, d.b1, st)); }       // d W1 and d b1 = colsum(d pre)
         // BatchNorm 1 backward (models.py:27): DA = d x -> DB = d h1 (= d h through the skip, = d GATConv output)
         { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);
-          GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_SUM_PROD, w.DA, h1, nullptr, M, 128, 0, w.CSP, &nb, st));
-          GNNGLS_TRY(gnngls::launch_bn_bwd_finalize(w.CSP, nb, M, p.bn1_g, bn, bn + 128, d.bn1_g, d.bn1_b, w.COEF, st)); }
+          GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_SUM_PROD, da, h1, nullptr, M, 128, 0, csp, &nb, st));
+          GNNGLS_TRY(gnngls::launch_bn_bwd_finalize(csp, nb, M, p.bn1_g, mean1, invstd1, d.bn1_g, d.bn1_b, coef, st)); }
         { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
-          GNNGLS_TRY(gnngls::launch_bn_bwd_apply(w.DA, h1, bn, w.COEF, w.DB, M, st)); }
-        // GATConv backward (models.py:23)
-        if (n_heads == 16) {        // per-head d el / d er: combine and attention-vector sums of their own
-          { ProfScope ps(GNNGLS_PROF_TRAIN_GAT_BWD, st);
-            GNNGLS_TRY(gnngls::launch_gat_heads_bwd_rows(ft, w.DB, g, att, p.attn_l, p.attn_r, B, n, n_heads, w.PART, w.PMS, st)); }
-          { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
-            GNNGLS_TRY(gnngls::launch_gat_heads_bwd_combine16(w.PART, w.PMS, p.attn_l, p.attn_r, M, w.DFT, w.DLR, w.DLR + (size_t)M * 16, st)); }
-          { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);
-            nb = gnngls::colsum_blocks(M, 128);
-            GNNGLS_TRY(gnngls::launch_colsum_heads16(ft, w.DLR, w.DLR + (size_t)M * 16, M, w.CSP, nb, st));
-            GNNGLS_TRY(gnngls::launch_colsum_store(w.CSP, nb, 128, 1, d.attn_l, d.attn_r, st)); }
-        } else {
-          { ProfScope ps(GNNGLS_PROF_TRAIN_GAT_BWD, st);
-            if (n_heads == 8) GNNGLS_TRY(gnngls::launch_gat_bwd_rows(ft, w.DB, g, att, p.attn_l, p.attn_r, B, n, w.PART, w.PMS, st));
-            else GNNGLS_TRY(gnngls::launch_gat_heads_bwd_rows(ft, w.DB, g, att, p.attn_l, p.attn_r, B, n, n_heads, w.PART, w.PMS, st)); }
-          { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
-            GNNGLS_TRY(gnngls::launch_gat_bwd_combine(w.PART, w.PMS, p.attn_l, p.attn_r, M, w.DFT, w.DLR, w.DLR + (size_t)M * 8, st)); }
-          { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);
-            GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_HEADSCALE, ft, w.DLR, w.DLR + (size_t)M * 8, M, 128, 0, w.CSP, &nb, st));
-            GNNGLS_TRY(gnngls::launch_colsum_store(w.CSP, nb, 128, 1, d.attn_l, d.attn_r, st)); }
-        }
+          GNNGLS_TRY(gnngls::launch_bn_bwd_apply(da, h1, mean1, coef, db, M, st)); }
+        // GATConv backward (models.py:23): attention backward, combine, the attn_l / attn_r column sums (d el / d er per slot, or
+        // with 16 heads per head: combine and sums of their own)
+        { ProfScope ps(GNNGLS_PROF_TRAIN_GAT_BWD, st);
+          GNNGLS_TRY(launch_attention_bwd(plan.bwd, ft, db, g, att, p.attn_l, p.attn_r, B, n, part, pms, st)); }
+        { ProfScope ps(GNNGLS_PROF_TRAIN_ELEMENTWISE, st);
+          GNNGLS_TRY(launch_attention_bwd_combine(plan.combine, part, pms, p.attn_l, p.attn_r, M, dft, dl, dr, st)); }
+        { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);
+          if (plan.combine == gnngls::COMBINE_HEADS16) {
+              nb = gnngls::colsum_blocks(M, 128);
+              GNNGLS_TRY(gnngls::launch_colsum_heads16(ft, dl, dr, M, csp, nb, st));
+          } else GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_HEADSCALE, ft, dl, dr, M, 128, 0, csp, &nb, st));
+          GNNGLS_TRY(gnngls::launch_colsum_store(csp, nb, 128, 1, d.attn_l, d.attn_r, st)); }
         { ProfScope ps(GNNGLS_PROF_TRAIN_GEMM_TN, st);
-          GNNGLS_TRY(gnngls::launch_gemm_tn(w.DFT, h, M, 128, 128, w.TNP, d.fc_w, nullptr, st)); }
+          GNNGLS_TRY(gnngls::launch_gemm_tn(dft, h, M, 128, 128, tnp, d.fc_w, nullptr, st)); }
         { ProfScope ps(GNNGLS_PROF_TRAIN_GEMM_BWD, st);      // d h = d ft * Wfc + d h1 (skip, models.py:15)
-          GNNGLS_TRY(gnngls::launch_gemm_wkn(gnngls::GEMM_EPI_ADD, w.DFT, p.fc_w, w.DA, M, 128, 128, w.DB, st)); }
+          GNNGLS_TRY(gnngls::launch_gemm_wkn(gnngls::GEMM_EPI_ADD, dft, p.fc_w, da, M, 128, 128, db, st)); }
     }
     // embedding (models.py:66): h0 = x We^T + be
     { ProfScope ps(GNNGLS_PROF_TRAIN_COLSUM, st);
       for (int d = 0; d < in_dim; ++d) {
-          GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_ROWSCALE, w.DA, feat + d, nullptr, M, 128, in_dim, w.CSP, &nb, st));
-          GNNGLS_TRY(gnngls::launch_colsum_store(w.CSP, nb, 128, in_dim, g_emb_w + d, d == 0 ? g_emb_b : nullptr, st));
+          GNNGLS_TRY(gnngls::launch_colsum(gnngls::CS_ROWSCALE, da, feat + d, nullptr, M, 128, in_dim, csp, &nb, st));
+          GNNGLS_TRY(gnngls::launch_colsum_store(csp, nb, 128, in_dim, g_emb_w + d, d == 0 ? g_emb_b : nullptr, st));
       } }
     return GNNGLS_OK;
 }

@@ -6,7 +6,6 @@
 
 namespace gnngls {
 
-size_t gat_heads_bwd_lds_bytes(int n, int n_heads);
 // attention partials of every row: `part` [2][B N][128] by side; statistics into part_ms [2][B N][8 + 8] per 16-column slot
 // (H <= 4) or into hms [2][B N][16 + 16] per head (H = 16, then launch_gat_heads_merge16 before the feed-forward launch);
 // waves: gat_heads_rows_step() of the plan
@@ -18,9 +17,10 @@ hipError_t launch_gat_heads_merge16(float *part, const float *hms, float *part_m
 hipError_t launch_gat_heads_merge16_train(const float *part, const float *hms, const float *h, long M, float *g, float *h1, float *att,
                                           hipStream_t st);
 // GATConv backward: P [2][B N][128]; d el / d er into dlr [2][B N][8 + 8] per slot (H <= 4: launch_gat_bwd_combine) or
-// [2][B N][16 + 16] per head (H = 16: launch_gat_heads_bwd_combine16); att in the layout its forward wrote
+// [2][B N][16 + 16] per head (H = 16: launch_gat_heads_bwd_combine16); att in the layout its forward wrote; lds: the plan's
+// (gat_heads_bwd_lds_bytes of model_policy.h)
 hipError_t launch_gat_heads_bwd_rows(const float *ft, const float *dout, const float *gout, const float *att, const float *attn_l,
-                                     const float *attn_r, int B, int n, int n_heads, float *P, float *dlr, hipStream_t st);
+                                     const float *attn_r, int B, int n, int n_heads, size_t lds, float *P, float *dlr, hipStream_t st);
 hipError_t launch_gat_heads_bwd_combine16(const float *P, const float *dlr, const float *attn_l, const float *attn_r, long M,
                                           float *dft, float *dl, float *dr, hipStream_t st);
 // H = 16: the attn_l / attn_r gradient column sums (dl / dr [M][16]) into colsum partials of nblocks = colsum_blocks(M, 128)

@@ -306,17 +306,10 @@ __global__ void gat_heads_merge16_kernel(float *part, const float *__restrict__ 
 // Outputs: P [2][M][128] by side; d el / d er into `dlr` in the layout of the consumers: F >= 16 the slot layout [2][M][8 + 8]
 // of gat_bwd_combine_kernel (replicated over the head's slots), F = 8 per head [2][M][16 + 16] (gat_heads_bwd_combine16_kernel).
 // ---------------------------------------------------------------------------------------------
-template <int F>
-struct BwdShape {
-    static constexpr int CW = F == 128 ? 128 : 64;       // dOut columns staged per workgroup
-    static constexpr int HB = CW / F;                    // heads per workgroup: 1, 1, 2, 8
-    static constexpr int WS = HB >= 4 ? 1 : 4 / HB;      // wavefronts per head: 4, 4, 2, 1
-    static constexpr int WAVES = HB * WS;                // 4, 4, 4, 8
-    static constexpr int LDG = CW + 4;                   // LDS row stride (floats)
-    static constexpr int KB = F >= 16 ? F / 16 : 1;      // 16-feature blocks of a head
-    static constexpr int LP = F >= 16 ? F / 16 : 1;      // lanes per (slot, head) in the statistics pass
-    static constexpr int ATS = F >= 16 ? 16 : 32;        // att row stride: slot layout (8 + 8) or per head (16 + 16)
-};
+// The workgroup shape BwdShape<F> and the LDS carve below (heads_bwd_lds<F>) are model_policy.h's, shared with the plan.
+static_assert(BwdShape<128>::WAVES * 64 <= 512 && BwdShape<64>::WAVES * 64 <= 512 && BwdShape<32>::WAVES * 64 <= 512 &&
+              BwdShape<8>::WAVES * 64 <= 512, "gat_heads_bwd_rows_kernel's launch bound");
+static_assert(BwdShape<128>::LDG % 4 == 0 && BwdShape<64>::LDG % 4 == 0, "16-byte LDS rows");
 
 template <int F>
 __global__ __launch_bounds__(512) void gat_heads_bwd_rows_kernel(const float *__restrict__ ft, const float *__restrict__ dout,
@@ -538,22 +531,6 @@ static_assert(HeadShape<128>::UNITS == 2 && HeadShape<64>::UNITS == 1 && HeadSha
               "gat_heads_rows_units() counts the 64-column units of a workgroup");
 
 template <int F>
-static size_t heads_bwd_lds(int n) {
-    using S = BwdShape<F>;
-    const size_t ns = (size_t)n - 1;
-    return ns * S::HB * 16 + ns * S::LDG * 4 + ns * S::HB * 4 + (size_t)S::WAVES * ns * 4 + ns * 4 + 16;
-}
-
-size_t gat_heads_bwd_lds_bytes(int n, int n_heads) {
-    switch (n_heads) {
-    case 1: return heads_bwd_lds<128>(n);
-    case 2: return heads_bwd_lds<64>(n);
-    case 4: return heads_bwd_lds<32>(n);
-    default: return heads_bwd_lds<8>(n);
-    }
-}
-
-template <int F>
 static hipError_t launch_rows(const float *ft, const float *attn_l, const float *attn_r, int B, int n, int waves, float *part,
                               float *part_ms, float *hms, hipStream_t st) {
     using S = HeadShape<F>;
@@ -596,9 +573,9 @@ hipError_t launch_gat_heads_merge16_train(const float *part, const float *hms, c
 
 template <int F>
 static hipError_t launch_bwd(const float *ft, const float *dout, const float *gout, const float *att, const float *attn_l,
-                             const float *attn_r, int B, int n, float *P, float *dlr, hipStream_t st) {
+                             const float *attn_r, int B, int n, size_t lds, float *P, float *dlr, hipStream_t st) {
     using S = BwdShape<F>;
-    const size_t lds = heads_bwd_lds<F>(n);
+    if (lds != heads_bwd_lds<F>(n)) return hipErrorInvalidValue;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(gat_heads_bwd_rows_kernel<F>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -609,13 +586,13 @@ static hipError_t launch_bwd(const float *ft, const float *dout, const float *go
 }
 
 hipError_t launch_gat_heads_bwd_rows(const float *ft, const float *dout, const float *gout, const float *att, const float *attn_l,
-                                     const float *attn_r, int B, int n, int n_heads, float *P, float *dlr, hipStream_t st) {
+                                     const float *attn_r, int B, int n, int n_heads, size_t lds, float *P, float *dlr, hipStream_t st) {
     if (n < 3 || n > kMaxNodes) return hipErrorInvalidValue;
     switch (n_heads) {
-    case 1: return launch_bwd<128>(ft, dout, gout, att, attn_l, attn_r, B, n, P, dlr, st);
-    case 2: return launch_bwd<64>(ft, dout, gout, att, attn_l, attn_r, B, n, P, dlr, st);
-    case 4: return launch_bwd<32>(ft, dout, gout, att, attn_l, attn_r, B, n, P, dlr, st);
-    case 16: return launch_bwd<8>(ft, dout, gout, att, attn_l, attn_r, B, n, P, dlr, st);
+    case 1: return launch_bwd<128>(ft, dout, gout, att, attn_l, attn_r, B, n, lds, P, dlr, st);
+    case 2: return launch_bwd<64>(ft, dout, gout, att, attn_l, attn_r, B, n, lds, P, dlr, st);
+    case 4: return launch_bwd<32>(ft, dout, gout, att, attn_l, attn_r, B, n, lds, P, dlr, st);
+    case 16: return launch_bwd<8>(ft, dout, gout, att, attn_l, attn_r, B, n, lds, P, dlr, st);
     default: return hipErrorInvalidValue;
     }
 }

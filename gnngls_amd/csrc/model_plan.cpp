@@ -1,4 +1,4 @@
-// model_plan.cpp -- the regret forward's plan: plain host C++ (no HIP call, no global, no environment), see model_plan.h.
+// model_plan.cpp -- the plans of the regret forward and of the training step: plain host C++ (no HIP call, no global, no environment), see model_plan.h.
 #include "model_plan.h"
 
 #include "../../include/gnngls_hip.h"
@@ -96,6 +96,64 @@ ForwardPlan forward_plan(const ForwardRequest &r) {
     };
     p.first = step(true, r.n_layers == 1); p.middle = step(false, false); p.last = step(false, true);
     p.decision_launch = !(prep && r.n_layers > 0);
+    return p;
+}
+
+TrainLayout train_layout(long M, int n_layers, int n_heads) {
+    TrainLayout w;
+    size_t p = 0;
+    auto take = [&p](size_t bytes) { const size_t q = p; p = (p + bytes + 255) & ~(size_t)255; return q; };
+    const size_t L = (size_t)n_layers, fl = sizeof(float);
+    w.M = M; w.row = (size_t)M * kD * fl; w.stat_w = n_heads == 16 ? 32 : 16;
+    const size_t stats = (size_t)M * w.stat_w * fl, dlr = stats / 2, wt = (size_t)kFfnHidden * kD * fl;
+    w.H = take(w.row * (L + 1)); w.FT = take(w.row * L); w.G = take(w.row * L); w.H1 = take(w.row * L); w.H3 = take(w.row * L);
+    w.HID = take(4 * w.row * L); w.ATT = take(stats * L); w.BN = take(L * BN_SLOTS * kD * fl);
+    w.PART = take(2 * w.row); w.PMS = take(2 * stats);
+    w.DA = take(w.row); w.DB = take(w.row); w.X2 = take(w.row); w.DFT = take(w.row);
+    w.DL = take(2 * dlr); w.DR = w.DL + dlr;
+    w.W2T = take(2 * wt); w.W1T = w.W2T + wt;
+    w.COEF = take((3 * kD + kD + kFfnHidden) * fl); w.ONES = w.COEF + 3 * kD * fl; w.ZEROS = w.ONES + kD * fl;
+    w.CSP = take((size_t)kColsumMaxBlocks * 2 * kFfnHidden * sizeof(double));
+    w.TNP = take((size_t)gemm_tn_chunks(M) * (kD * kFfnHidden + kFfnHidden) * fl);
+    w.end = p;
+    return w;
+}
+
+int64_t train_workspace_bytes(int B, int n, int n_layers, int n_heads) {
+    if (!heads_supported(n_heads)) return 0;
+    if (B < 1 || n < 2 || n > 65535 || n_layers < 0 || n_layers > 4096) return 0;
+    return (int64_t)train_layout((long)B * ((long)n * (n - 1) / 2), n_layers, n_heads).end + 256;
+}
+
+namespace {
+template <int F>
+AttnBwdStep heads_bwd_step(int n) {
+    using S = BwdShape<F>;
+    return {ATTN_K1H, 0, F, heads_bwd_lds<F>(n), kD / S::CW, S::WAVES};
+}
+}  // namespace
+
+TrainPlan train_plan(const TrainRequest &r) {
+    TrainPlan p{};
+    p.status = GNNGLS_OK; p.why = TRAIN_OK;
+    auto refuse = [&p](int status, TrainRefusal why, int64_t number) { p.status = status; p.why = why; p.number = number; return p; };
+    if (!heads_supported(r.n_heads)) return refuse(GNNGLS_ERR_UNSUPPORTED, TRAIN_BAD_HEADS, r.n_heads);
+    if (!r.pointers_given || r.B < 1 || r.n < 3 || r.in_dim < 1 || r.n_layers < 0) return refuse(GNNGLS_ERR_ARG, TRAIN_BAD_ARG, 0);
+    // the backward's register-resident accumulators set the limit; no LDS refusal below it (model_policy.h asserts every carve)
+    if (r.n > kTrainMaxNodes) return refuse(GNNGLS_ERR_UNSUPPORTED, TRAIN_BWD_NODES, kTrainMaxNodes);
+    // (as the ABI's size query answers: 0, and so no refusal here, beyond 4096 layers)
+    const int64_t need = train_workspace_bytes(r.B, r.n, r.n_layers, r.n_heads);
+    if (r.workspace_bytes < need) return refuse(GNNGLS_ERR_ARG, TRAIN_WORKSPACE_SMALL, need);
+    p.ws = train_layout((long)r.B * ((long)r.n * (r.n - 1) / 2), r.n_layers, r.n_heads);
+    p.attn = r.n_heads == 8 ? gat_rows_step(r.n, r.gat_heads) : gat_heads_rows_step(r.n, r.n_heads);
+    p.combine = r.n_heads == 16 ? COMBINE_HEADS16 : COMBINE_SLOTS;
+    switch (r.n_heads) {
+    case 8: p.bwd = {ATTN_K1, gat_bwd_tiles(r.n), kF, gat_bwd_lds_bytes(r.n), kH / kGatBwdHeads, kGatBwdHeads}; break;
+    case 1: p.bwd = heads_bwd_step<128>(r.n); break;
+    case 2: p.bwd = heads_bwd_step<64>(r.n); break;
+    case 4: p.bwd = heads_bwd_step<32>(r.n); break;
+    default: p.bwd = heads_bwd_step<8>(r.n); break;
+    }
     return p;
 }
 

@@ -1,6 +1,7 @@
-// model_policy.h -- what the regret model's kernels (model_kernels.hip, heads_kernels.hip) and the forward's plan (model_plan.cpp:
-// plain host C++) both need: the model's dimensions, the LDS carve of each attention kernel and the launch-shape rules measured on
-// them.  constexpr only, no HIP include; a kernel file asserts the relations it relies on.
+// model_policy.h -- what the regret model's kernels (model_kernels.hip, heads_kernels.hip, train_kernels.hip) and the plans of the
+// forward and of the training step (model_plan.cpp: plain host C++) both need: the model's dimensions, the LDS carve of each
+// attention kernel, forward and backward, the launch-shape rules measured on them and the grids of the training step's reductions.
+// constexpr only, no HIP include; a kernel file asserts the relations it relies on.
 #pragma once
 #include <stddef.h>
 
@@ -81,6 +82,71 @@ constexpr int gat_heads_rows_waves(int units) {
     for (int w = 5; w <= 8; ++w)
         if (idle_wave_slots(units, w) < idle_wave_slots(units, waves)) waves = w;
     return waves;
+}
+
+// ---- K1 backward: gat_bwd_rows_kernel<MAXT> (train_kernels.hip), 8 heads of 16 features, kGatBwdHeads of them per workgroup -------
+constexpr int kGatBwdHeads = 2;                    // heads per workgroup (one wave each): the LDS tile of a workgroup covers
+                                                   // 16*kGatBwdHeads columns of ft / dOut, so several workgroups share a CU
+                                                   // and the staging of one overlaps the MFMA phase of the others
+constexpr int kGatBwdThreads = 64 * kGatBwdHeads;
+constexpr int kGatBwdMaxTiles = 16;                // 16-node source tiles per row the largest instantiation holds: n - 1 <= 256
+constexpr int kGatBwdRowStride = 16 * kGatBwdHeads + 4;   // LDS row stride (floats): a ds_read_b128 of 16 consecutive rows at one
+                                                   // column offset touches 16 disjoint groups of 4 banks; 4 rows 4 apart
+                                                   // (MFMA B fragment) land on disjoint 16-bank groups  (36, 68, 132)
+constexpr int kGatBwdMaxNodes = 16 * kGatBwdMaxTiles + 1;  // register-resident accumulators: one per 16-node source tile
+constexpr size_t gat_bwd_lds_bytes(int n) {
+    const size_t ns = (size_t)n - 1;
+    return 2 * ns * kGatBwdRowStride * 4 + ns * kGatBwdHeads * 4 + ns * kGatBwdHeads * 16 + ns * 4 + 16;
+}
+// source tiles the instantiation keeps accumulators for (5 VGPRs each): the smallest of 9 (n <= 145, the reference's training
+// sizes up to TSP100), 13 (n <= 209: TSP200) and 16 (n <= 257) that covers n
+constexpr int gat_bwd_tiles(int n) { return (n - 1 + 15) / 16 <= 9 ? 9 : (n - 1 + 15) / 16 <= 13 ? 13 : kGatBwdMaxTiles; }
+
+// ---- K1h backward: gat_heads_bwd_rows_kernel<F> (heads_kernels.hip) ----------------------------------------------------------------
+template <int F>
+struct BwdShape {
+    static constexpr int CW = F == 128 ? 128 : 64;       // dOut columns staged per workgroup
+    static constexpr int HB = CW / F;                    // heads per workgroup: 1, 1, 2, 8
+    static constexpr int WS = HB >= 4 ? 1 : 4 / HB;      // wavefronts per head: 4, 4, 2, 1
+    static constexpr int WAVES = HB * WS;                // 4, 4, 4, 8
+    static constexpr int LDG = CW + 4;                   // LDS row stride (floats)
+    static constexpr int KB = F >= 16 ? F / 16 : 1;      // 16-feature blocks of a head
+    static constexpr int LP = F >= 16 ? F / 16 : 1;      // lanes per (slot, head) in the statistics pass
+    static constexpr int ATS = F >= 16 ? 16 : 32;        // att row stride: slot layout (8 + 8) or per head (16 + 16)
+};
+template <int F>
+constexpr size_t heads_bwd_lds(int n) {
+    using S = BwdShape<F>;
+    const size_t ns = (size_t)n - 1;
+    return ns * S::HB * 16 + ns * S::LDG * 4 + ns * S::HB * 4 + (size_t)S::WAVES * ns * 4 + ns * 4 + 16;
+}
+constexpr size_t gat_heads_bwd_lds_bytes(int n, int n_heads) {
+    return n_heads == 1 ? heads_bwd_lds<128>(n) : n_heads == 2 ? heads_bwd_lds<64>(n) : n_heads == 4 ? heads_bwd_lds<32>(n)
+                                                                                                       : heads_bwd_lds<8>(n);
+}
+
+// ---- the training step's limit is the backward's, and there every carve (monotone in n) leaves room: no LDS refusal in the step ----
+constexpr int kTrainMaxNodes = kGatBwdMaxNodes;
+static_assert(kTrainMaxNodes <= kMaxNodes, "the K1h kernels (forward and backward) hold n - 1 <= 256 sources per row");
+static_assert(gat_rows_lds_bytes(kTrainMaxNodes) <= kModelLdsPerCU && gat_bwd_lds_bytes(kTrainMaxNodes) <= kModelLdsPerCU,
+              "8 heads: the K1 forward and backward tiles fit a CU's LDS up to the training limit");
+static_assert(heads_rows_lds<128>(kTrainMaxNodes) <= kModelLdsPerCU && heads_rows_lds<64>(kTrainMaxNodes) <= kModelLdsPerCU &&
+              heads_rows_lds<32>(kTrainMaxNodes) <= kModelLdsPerCU && heads_rows_lds<8>(kTrainMaxNodes) <= kModelLdsPerCU,
+              "1, 2, 4, 16 heads: the K1h forward tile fits a CU's LDS up to the training limit");
+static_assert(heads_bwd_lds<128>(kTrainMaxNodes) <= kModelLdsPerCU && heads_bwd_lds<64>(kTrainMaxNodes) <= kModelLdsPerCU &&
+              heads_bwd_lds<32>(kTrainMaxNodes) <= kModelLdsPerCU && heads_bwd_lds<8>(kTrainMaxNodes) <= kModelLdsPerCU,
+              "1, 2, 4, 16 heads: the K1h backward tile fits a CU's LDS up to the training limit");
+
+// ---- grids of the training step's reductions (train_kernels.hip); the workspace holds their partials -----------------------------
+constexpr int kColsumMaxBlocks = 512;     // partial buffer: kColsumMaxBlocks * 2 * 512 doubles
+constexpr int kGemmTnMaxChunks = 256;     // partial buffer: kGemmTnMaxChunks * (128 * 512 + 512) floats
+constexpr int colsum_blocks(long M, int C) {            // 16 rows per row lane of a block, 1024 / C row lanes
+    const long rows = 1024 / C * 16, want = (M + rows - 1) / rows;
+    return (int)(want > kColsumMaxBlocks ? kColsumMaxBlocks : want < 1 ? 1 : want);
+}
+constexpr int gemm_tn_chunks(long M) {                  // >= 128 rows (4 k-tiles) per chunk, at most kGemmTnMaxChunks chunks
+    const long want = (M + 127) / 128;
+    return (int)(want > kGemmTnMaxChunks ? kGemmTnMaxChunks : want < 1 ? 1 : want);
 }
 
 }  // namespace gnngls

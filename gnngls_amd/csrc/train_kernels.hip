@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "model_policy.h"
 #include "train_kernels.h"
 
 namespace gnngls {
@@ -31,7 +32,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-constexpr int kD = 128, kH = 8, kF = 16;
 constexpr float kSlope = 0.2f;
 
 __device__ __forceinline__ int tri_index(int i, int j, int n) {   // i < j, rank in itertools.combinations order
@@ -289,14 +289,12 @@ __global__ void gat_combine_train_kernel(const float *__restrict__ part, const f
 // written to side (u < k ? 0 : 1) of the partial buffers; the other endpoint's row supplies the second half.
 // gat_bwd_combine_kernel then forms  dft = P + del*attn_l + der*attn_r  (el = <ft,attn_l>, er = <ft,attn_r>).
 // ---------------------------------------------------------------------------------------------
-constexpr int kGatBwdHeads = 2;                    // heads per workgroup (one wave each): the LDS tile of a workgroup covers
-                                                   // 16*kGatBwdHeads columns of ft / dOut, so several workgroups share a CU
-                                                   // and the staging of one overlaps the MFMA phase of the others
-constexpr int kGatBwdThreads = 64 * kGatBwdHeads;
-constexpr int kGatBwdMaxTiles = 16;                // 16-node source tiles per row the largest instantiation holds: n - 1 <= 256
-constexpr int LDG = 16 * kGatBwdHeads + 4;         // LDS row stride (floats): a ds_read_b128 of 16 consecutive rows at one
-                                                   // column offset touches 16 disjoint groups of 4 banks; 4 rows 4 apart
-                                                   // (MFMA B fragment) land on disjoint 16-bank groups  (36, 68, 132)
+// The workgroup shape, the LDS carve below and the limit are model_policy.h's (kGatBwd*, gat_bwd_lds_bytes), shared with the plan.
+static_assert(kH % kGatBwdHeads == 0 && kGatBwdThreads == 64 * kGatBwdHeads, "one wave per head of the workgroup's head group");
+static_assert(kGatBwdRowStride % 4 == 0 && kGatBwdRowStride >= kGatBwdHeads * kF, "16-byte LDS rows that hold the head group's columns");
+static_assert(gat_bwd_tiles(3) == 9 && gat_bwd_tiles(145) == 9 && gat_bwd_tiles(146) == 13 && gat_bwd_tiles(209) == 13 &&
+              gat_bwd_tiles(210) == 16 && gat_bwd_tiles(kGatBwdMaxNodes) == kGatBwdMaxTiles,
+              "gat_bwd_tiles() names the instantiations of gat_bwd_rows_kernel that launch_gat_bwd_rows knows");
 
 __device__ __forceinline__ float row16_sum(float v) {   // inclusive prefix over the 16-lane DPP row; lane 15 holds the total
     v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xf, 0xf, true));   // row_shr:1
@@ -322,7 +320,7 @@ __global__ __launch_bounds__(kGatBwdThreads) void gat_bwd_rows_kernel(const floa
                                                                       const float *__restrict__ attn_l, const float *__restrict__ attn_r,
                                                                       int n, float *__restrict__ P, float *__restrict__ dlr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int HG = kGatBwdHeads, CW = 16 * HG;                // heads / columns per workgroup
+    constexpr int HG = kGatBwdHeads, CW = 16 * HG, LDG = kGatBwdRowStride;   // heads / columns per workgroup, LDS row stride
     constexpr int groups = kH / HG;
     const int N = n * (n - 1) / 2;
     const int ns = n - 1, nt = (ns + 15) >> 4;
@@ -618,11 +616,6 @@ __global__ __launch_bounds__(256) void gemm_tn_reduce_kernel(const float *__rest
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
-int colsum_blocks(long M, int C) {
-    const int rl = 1024 / C;
-    return grid_cap((M + (long)rl * 16 - 1) / ((long)rl * 16), kColsumMaxBlocks);
-}
-
 hipError_t launch_colsum(int mode, const float *X, const float *Y, const float *Y2, long M, int C, int ystride,
                          double *partial, int *nblocks, hipStream_t st) {
     const int nb = colsum_blocks(M, C);
@@ -704,19 +697,11 @@ hipError_t launch_gat_combine_train(const float *part, const float *part_ms, con
     return hipGetLastError();
 }
 
-int gat_bwd_max_nodes() { return 16 * kGatBwdMaxTiles + 1; }   // register-resident accumulators: one per 16-node source tile
-
-size_t gat_bwd_lds_bytes(int n) {
-    const size_t ns = (size_t)n - 1, nt = (ns + 15) / 16, nsp = nt * 16;
-    (void)nt; (void)nsp;
-    return 2 * ns * LDG * 4 + ns * kGatBwdHeads * 4 + ns * kGatBwdHeads * 16 + ns * 4 + 16;
-}
-
+// tiles (9, 13 or 16: the instantiation) and lds: gat_bwd_tiles() / gat_bwd_lds_bytes() of the plan
 hipError_t launch_gat_bwd_rows(const float *ft, const float *dout, const float *gout, const float *att, const float *attn_l,
-                               const float *attn_r, int B, int n, float *P, float *dlr, hipStream_t st) {
-    const size_t lds = gat_bwd_lds_bytes(n);
-    const int nt = (n - 1 + 15) / 16;
-    auto kern = nt <= 9 ? gat_bwd_rows_kernel<9> : nt <= 13 ? gat_bwd_rows_kernel<13> : gat_bwd_rows_kernel<16>;
+                               const float *attn_r, int B, int n, int tiles, size_t lds, float *P, float *dlr, hipStream_t st) {
+    if (n < 3 || n > kGatBwdMaxNodes || (n - 1 + 15) / 16 > tiles || lds != gat_bwd_lds_bytes(n)) return hipErrorInvalidValue;
+    auto kern = tiles == 9 ? gat_bwd_rows_kernel<9> : tiles == 13 ? gat_bwd_rows_kernel<13> : gat_bwd_rows_kernel<16>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     (void)hipGetLastError();
@@ -730,11 +715,6 @@ hipError_t launch_gat_bwd_combine(const float *P, const float *dlr, const float 
     (void)hipGetLastError();
     hipLaunchKernelGGL(gat_bwd_combine_kernel, dim3(ew_grid(M)), dim3(256), 0, st, P, dlr, attn_l, attn_r, M, dft, dl, dr);
     return hipGetLastError();
-}
-
-int gemm_tn_chunks(long M) {           // >= 128 rows (4 k-tiles) per chunk, at most kGemmTnMaxChunks chunks
-    long c = (M + 127) / 128;
-    return grid_cap(c, kGemmTnMaxChunks);
 }
 
 hipError_t launch_gemm_tn(const float *X, const float *Y, long M, int N1, int N2, float *partial, float *out,
