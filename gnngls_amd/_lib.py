@@ -14,6 +14,7 @@ _int = ctypes.c_int
 _i64 = ctypes.c_int64
 _f64 = ctypes.c_double
 _f32 = ctypes.c_float
+_u64 = ctypes.c_uint64
 
 # name -> argtypes; every function returns int (0 = ok) unless listed in _RESTYPES
 SIGNATURES = {
@@ -32,6 +33,7 @@ SIGNATURES = {
     "gnngls_cheapest_insertion": [_vp, _int, _vp, _vp, _int, _int, _vp, _vp, _vp],
     "gnngls_one_tree_bound": [_vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],
     "gnngls_one_tree_bound_describe": [_int, _vp, _vp, _vp],
+    "gnngls_sample_nn_tours": [_vp, _int, _int, _int, _int, _int, _u64, _vp, _vp, _vp, _vp],
     "gnngls_gls_run": [_vp, _vp, _int, _int, _int, _vp, _vp, _int, _int, _int, _i64, _f64, _f64,
                        _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp],
     "gnngls_model_packed_floats": [_int, _int],
@@ -103,6 +105,8 @@ _HEADS = ("gnngls_model_heads_supported", "gnngls_regret_forward_workspace_bytes
 _CONSTRUCTORS = ("gnngls_insertion", "gnngls_cheapest_insertion")
 # the Held-Karp 1-tree bound (an older build named by GNNGLS_HIP_SO lacks it; ops.one_tree_bound then raises)
 _BOUNDS = ("gnngls_one_tree_bound", "gnngls_one_tree_bound_describe")
+# the sampled nearest-neighbour walks (an older build named by GNNGLS_HIP_SO lacks them; ops.sample_nn_tours then raises)
+_SAMPLING = ("gnngls_sample_nn_tours",)
 _lib = None
 
 
@@ -125,7 +129,7 @@ def load():
         import torch  # noqa: F401
         L = ctypes.CDLL(SO)
         for name, argtypes in SIGNATURES.items():
-            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS or name in _BOUNDS) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
+            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS or name in _BOUNDS or name in _SAMPLING) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
                 continue              # an older build of the library named by GNNGLS_HIP_SO (same-box A/B of kernel variants)
             f = getattr(L, name)      # AttributeError if the symbol is missing
             f.argtypes = argtypes

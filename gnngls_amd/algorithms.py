@@ -1,9 +1,13 @@
-"""Mirror of gnngls/algorithms.py (reference algorithms.py:9-18,67-195): `nearest_neighbor`, `cheapest_insertion`,
+"""Mirror of gnngls/algorithms.py (reference algorithms.py:9-195): `nearest_neighbor`, `cheapest_insertion`,
 `insertion`, `local_search`, `guided_local_search` with the reference's signatures, return values and side
 effects, executed by the HIP kernels (the persistent search kernel, the one-launch insertion constructor).
 
-The probabilistic constructors (algorithms.py:21-64) stay out of scope: their result depends on NumPy's internal
-pairwise summation (`np.sum(p)`) and on draws that interleave with the state of the walk.
+The probabilistic constructors (algorithms.py:21-64: `probabilistic_nearest_neighbour`, `best_probabilistic_nearest_neighbour`)
+have the reference's signatures plus a trailing `seed` and the reference's LAW, not its draws: np.random.choice draws from NumPy's
+stream against a pairwise `np.sum(p)`, the sampling kernel draws from Philox4x32-10 against the fixed summation order
+include/gnngls_hip.h states.  Given the uniforms a walk is pinned bit for bit (ops.sample_nn_tours(u=...)); the distribution
+over tours is the reference's (tests/golden/pnn_law_n6.npz).  seed=None takes the seed as ONE draw from NumPy's global stream,
+so np.random.seed(k) makes a run repeatable as it does in the reference (the stream advances by one draw, not by n - 1).
 """
 import time
 import warnings
@@ -61,6 +65,35 @@ def insertion(G, depot, mode="farthest", weight="weight"):
     assert mode in ['random', 'nearest', 'farthest'], f'Unknown mode: {mode}'
     W = ops.as_dev(_attr_matrix(G, weight)[None], torch.float64)
     return ops.insertion(W, depot, mode)[0].tolist()
+
+
+def _draw_seed(seed):
+    return int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64)) if seed is None else int(seed)
+
+
+def probabilistic_nearest_neighbour(G, depot, guide='weight', invert=True, seed=None):
+    """algorithms.py:21-50: a nearest-neighbour walk whose next node is drawn with probability proportional to the guide (invert:
+    to its reciprocal) among the unvisited ones.  Weights np.random.choice refuses raise ValueError as there."""
+    n = len(G.nodes)
+    seed = _draw_seed(seed)
+    if n < 3:                                                                    # nothing to draw: one candidate per step
+        return [depot] + [j for j in range(n) if j != depot] + [depot]
+    W = ops.as_dev(_attr_matrix(G, guide)[None], torch.float64)
+    return ops.sample_nn_tours(W, 1, depot, invert, seed)[0][0, 0].tolist()
+
+
+def best_probabilistic_nearest_neighbour(G, depot, n_iters, guide='weight', weight='weight', seed=None):
+    """algorithms.py:53-64: the first strictly cheapest (tour_cost on `weight`) of n_iters walks on `guide`, inverted as the
+    reference's call leaves it; None for n_iters <= 0.  The walks are runs 0 .. n_iters-1 of one launch under `seed`."""
+    n = len(G.nodes)
+    seed = _draw_seed(seed)
+    if n_iters <= 0:
+        return None
+    if n < 3:
+        return [depot] + [j for j in range(n) if j != depot] + [depot]
+    W = ops.as_dev(_attr_matrix(G, guide)[None], torch.float64)
+    D = W if weight == guide else ops.as_dev(_attr_matrix(G, weight)[None], torch.float64)
+    return ops.best_sampled_tour(W, D, int(n_iters), depot, True, seed)[0][0].tolist()
 
 
 def _check_status(r, what):

@@ -20,6 +20,7 @@
 #include "labels_kernels.h"
 #include "model_kernels.h"
 #include "model_plan.h"
+#include "sampling_kernels.h"
 #include "train_kernels.h"
 
 namespace {
@@ -264,6 +265,25 @@ int gnngls_one_tree_bound_describe(int n, int *threads, int *lds_bytes, int *nod
     if (lds_bytes) *lds_bytes = gnngls::one_tree_lds_bytes(n);
     if (nodes_per_lane) *nodes_per_lane = t > 64 ? 4 : (n + 63) / 64;
     return GNNGLS_OK;
+}
+
+static_assert(GNNGLS_SAMPLE_MAX_N == gnngls::kSampleMaxN && GNNGLS_SAMPLE_BAD_WEIGHTS == GNNGLS_SAMPLE_BAD_WEIGHTS_DEV,
+              "include/gnngls_hip.h and sampling_kernels.h disagree");
+
+int gnngls_sample_nn_tours(const double *W, int B, int n, int R, int depot, int invert, uint64_t seed, const double *u,
+                           int32_t *tours, int32_t *status, void *stream) {
+    if (B < 0) return fail(GNNGLS_ERR_ARG, "sample_nn_tours: B=%d must be >= 0", B);
+    if (n < 3) return fail(GNNGLS_ERR_ARG, "sample_nn_tours: n=%d must be >= 3", n);
+    if (n > GNNGLS_SAMPLE_MAX_N)
+        return fail(GNNGLS_ERR_UNSUPPORTED, "sample_nn_tours: n=%d exceeds the largest supported instance (n <= %d: the state of a walk "
+                    "lives in the registers of one wavefront)", n, GNNGLS_SAMPLE_MAX_N);
+    if (R < 1) return fail(GNNGLS_ERR_ARG, "sample_nn_tours: R=%d must be >= 1", R);
+    if (depot < 0 || depot >= n) return fail(GNNGLS_ERR_ARG, "sample_nn_tours: depot=%d out of range (0..%d)", depot, n - 1);
+    if ((long long)B * R > 0x7fffffffLL) return fail(GNNGLS_ERR_ARG, "sample_nn_tours: B * R = %lld walks exceed 2^31 - 1", (long long)B * R);
+    if (B == 0) return GNNGLS_OK;
+    if (!W || !tours || !status) return fail(GNNGLS_ERR_ARG, "sample_nn_tours: NULL pointer (W, tours, status)");
+    hipError_t e = gnngls::launch_sample_nn_tours(W, B, n, R, depot, invert != 0, seed, u, tours, status, (hipStream_t)stream);
+    return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "sample_nn_tours");
 }
 
 int gnngls_gls_run(const double *D, const double *guides, int n_guides, int B, int n,

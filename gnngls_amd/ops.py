@@ -156,6 +156,64 @@ def cheapest_insertion(sub_tour, node, W):
     return out, cost
 
 
+SAMPLE_MAX_N = 1024                                           # GNNGLS_SAMPLE_MAX_N
+SAMPLE_BAD_WEIGHTS = 6                                        # GNNGLS_SAMPLE_BAD_WEIGHTS
+
+
+def sample_nn_launch(W, R, depot=0, invert=True, seed=0, u=None):
+    """The launch behind sample_nn_tours and torch.ops.gnngls.sample_nn_tours: -> (tours [B,R,n+1] int32, status [B,R] int32),
+    nothing raised for a walk that met bad weights (its status is SAMPLE_BAD_WEIGHTS, its tour -1)."""
+    B, n, n2 = W.shape
+    assert n == n2 and W.dtype == torch.float64
+    R = int(R)
+    if u is not None:
+        u = u.to(device=W.device, dtype=torch.float64).contiguous()
+        assert u.shape == (B, R, n - 1), f"u shape {tuple(u.shape)} is not [{B},{R},{n - 1}]"
+    tours = torch.empty((B, max(R, 0), n + 1), dtype=torch.int32, device=W.device)
+    status = torch.zeros((B, max(R, 0)), dtype=torch.int32, device=W.device)
+    L = _lib.load()
+    if not hasattr(L, "gnngls_sample_nn_tours"):
+        raise _lib.GnnglsHipError("this build of libgnngls_hip.so has no gnngls_sample_nn_tours")
+    _lib.check(L.gnngls_sample_nn_tours(_lib.ptr(W.contiguous()), B, n, R, int(depot), int(bool(invert)),
+                                        ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _lib.ptr(u), _lib.ptr(tours), _lib.ptr(status),
+                                        _lib.current_stream()), "sample_nn_tours")
+    return tours, status
+
+
+def sample_nn_tours(W, R, depot=0, invert=True, seed=0, u=None):
+    """R sampled nearest-neighbour walks per instance (reference algorithms.py:21-50, probabilistic_nearest_neighbour), one
+    launch, one wavefront per walk: W [B,n,n] fp64 -> (tours [B,R,n+1] int32, status [B,R] int32).  The next node is drawn with
+    probability proportional to W[i,j] (invert: to 1 / W[i,j]) among the unvisited ones; include/gnngls_hip.h states the walk
+    and the order of its sums.  u [B,R,n-1] fp64 in [0,1) gives the uniforms (the walks are then pinned bit for bit); None draws
+    them on the device from Philox4x32-10 keyed by `seed` with counter (b, r, step) -- not NumPy's stream: against the
+    reference the walks agree in law.  Weights np.random.choice would refuse (a zero under invert, NaN, negative) raise."""
+    tours, status = sample_nn_launch(W, R, depot, invert, seed, u)
+    bad = (status != 0).nonzero()
+    if bad.shape[0]:
+        raise ValueError(f"sample_nn_tours: walks (instance, run) {bad[:8].tolist()} met weights that are no probabilities "
+                         f"(NaN, negative, infinite or zero under invert; status {SAMPLE_BAD_WEIGHTS}): probabilities do not sum to 1")
+    return tours, status
+
+
+def first_argmin(x):
+    """[B,R] -> [B] int64 index of the first strictly smallest entry of every row."""
+    R = x.shape[1]
+    idx = torch.arange(R, device=x.device).expand_as(x)
+    return torch.where(x == x.min(dim=1, keepdim=True).values, idx, torch.full_like(idx, R)).min(dim=1).values
+
+
+def best_sampled_tour(W, D, R, depot=0, invert=True, seed=0, u=None):
+    """The first strictly cheapest of R sampled walks per instance under tour_cost on D (reference algorithms.py:53-64,
+    best_probabilistic_nearest_neighbour): W, D [B,n,n] fp64 -> (tour [B,n+1] int32, cost [B] fp64)."""
+    B, n, _ = W.shape
+    assert D.shape == W.shape and D.dtype == torch.float64
+    tours, _ = sample_nn_tours(W, R, depot, invert, seed, u)
+    cost = torch.stack([tour_cost(tours[:, r].contiguous(), D) for r in range(tours.shape[1])], dim=1)      # [B,R]
+    k = first_argmin(cost)
+    rows = torch.arange(B, device=W.device)
+    return tours[rows, k].contiguous(), cost[rows, k].contiguous()
+
+
 @dataclass
 class GlsResult:
     best_tour: torch.Tensor      # [B,n+1] int32

@@ -9,7 +9,13 @@ for B independent instances at once, entirely on the GPU.
 The 10 s budget of the reference starts before the forward pass (test.py:64), so the search gets
 `time_limit - elapsed`.  At most `gls_resident_capacity(n)` instances are searched concurrently (one
 persistent workgroup each); larger batches are processed in chunks, each with its own budget.
+
+Multi-start (`starts=R > 1`): every instance is searched R times in the same launch -- run 0 from the start tour above, runs
+1..R-1 from sampled nearest-neighbour walks on the distances (ops.sample_nn_tours, invert=True) -- and the first run with the
+smallest cost is the instance's result.  A chunk then holds capacity // R instances: a batch that leaves search slots idle
+fills them with further runs of its own instances instead.
 """
+import dataclasses
 import time
 import warnings
 from dataclasses import dataclass, field
@@ -72,6 +78,10 @@ class SolveResult:
     # certified lower_bound <= optimum <= best_cost, and how its ascent ended (ops.BOUND_EXIT_*; TOUR: the bound is the optimum)
     lower_bound: torch.Tensor = None   # [B] fp64
     bound_exit: torch.Tensor = None    # [B] int32
+    # only with starts = R > 1: the returned cost of every run (run 0 = the start tour `init`) and the run whose result the other
+    # per-instance fields carry: the first with the smallest cost
+    start_costs: torch.Tensor = None   # [B,R] fp64
+    best_start: torch.Tensor = None    # [B] int64
 
 
 # start tours of solve_batch -> mode of ops.insertion (None: ops.nearest_neighbor)
@@ -97,7 +107,7 @@ def predict_regret(model, D, scalers, features=None):
 def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit=10.0, perturbation_moves=20,
                 first_improvement=False, max_outer_iters=-1, trace_cap=0, want_trace_time=False, chunk=None,
                 keep_regret=False, budget="per_instance", imp_cap=0, features=None, count_executed=False,
-                init="nearest_neighbor", init_weight="auto", lower_bound=False, bound_iters=2000):
+                init="nearest_neighbor", init_weight="auto", lower_bound=False, bound_iters=2000, starts=1, start_seed=0):
     """D [B,n,n] fp64 CUDA tensor (symmetric).  Returns SolveResult with per-instance tensors.
 
     budget="per_instance" (default, the reference's meaning of --time_limit, test.py:64,92): every instance is searched
@@ -111,12 +121,19 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
     init_weight: the matrix the start tour is built on.  "auto" keeps the reference's rule (test.py:70-88: 'regret_pred'
     whenever that guide is used at all, else 'weight'); "weight" builds it on the distances even when the model guides the search.
     lower_bound: after a chunk's search has ended (outside its budget) also compute the Held-Karp 1-tree bound of its instances
-    with at most `bound_iters` 1-trees and ub = best_cost -> SolveResult.lower_bound, .bound_exit and timing["bound_s"]."""
+    with at most `bound_iters` 1-trees and ub = best_cost -> SolveResult.lower_bound, .bound_exit and timing["bound_s"].
+    starts: R > 1 searches every instance R times in one launch (run 0 from `init`, runs 1..R-1 from sampled walks on D keyed by
+    `start_seed` and the instance's index in the batch, so chunking does not change them) and returns the first run with the
+    smallest cost; a chunk holds capacity // R instances.  SolveResult.start_costs [B,R], .best_start [B], timing["sample_s"]
+    (the one sampling launch of the batch; its time is taken off the rounds' budgets in equal shares)."""
     if init not in INIT_TOURS:
         raise ValueError(f"unknown start tour {init!r} (one of {', '.join(INIT_TOURS)})")
     if init_weight not in ("auto", "weight"):
         raise ValueError(f"unknown init_weight {init_weight!r} ('auto' or 'weight')")
     insert_mode = INIT_TOURS[init]
+    starts = int(starts)
+    if starts < 1:
+        raise ValueError(f"starts={starts} must be >= 1")
     if budget not in ("per_instance", "per_batch"):
         raise ValueError(f"unknown budget policy {budget!r}")
     assert D.is_cuda and D.dtype == torch.float64
@@ -135,10 +152,11 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
                            init_cost=e64, outer_iters=ei64, evals=ei64, moves=ei32, status=ei32,
                            timing={"forward_s": 0.0, "init_s": 0.0, "search_s": 0.0, "chunks": 0},
                            start_time=e64.cpu(), launch_time=e64.cpu(), lower_bound=e64 if lower_bound else None,
-                           bound_exit=ei32 if lower_bound else None)
+                           bound_exit=ei32 if lower_bound else None,
+                           start_costs=e64.reshape(0, starts) if starts > 1 else None, best_start=ei64 if starts > 1 else None)
     cap = ops.gls_resident_capacity(n)
     if chunk is None:
-        chunk = cap if cap > 0 else 64
+        chunk = max((cap if cap > 0 else 64) // starts, 1)
         # equal-sized rounds: a batch a little larger than the device capacity is split evenly (same number of
         # rounds, i.e. the same wall time, but every round leaves the SIMDs less crowded)
         rounds = -(-B // chunk)
@@ -146,6 +164,13 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
     outs, timing = [], {"forward_s": 0.0, "init_s": 0.0, "search_s": 0.0, "chunks": 0}
     n_rounds = -(-B // chunk) if B > 0 else 1
     round_limit = time_limit / n_rounds if budget == "per_batch" else time_limit
+    sampled, sample_s = None, 0.0
+    if starts > 1:
+        ts = time.time()
+        sampled, _ = ops.sample_nn_tours(D, starts - 1, 0, True, start_seed)      # [B,R-1,n+1]: walk (b, r) belongs to instance b
+        torch.cuda.synchronize()
+        sample_s = time.time() - ts
+        timing["sample_s"] = sample_s
     for b0 in range(0, B, chunk):
         Dc = D[b0:b0 + chunk].contiguous()
         t0 = time.time()                                                   # test.py:64
@@ -161,18 +186,25 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
         init = ops.nearest_neighbor(Wi) if insert_mode is None else ops.insertion(Wi, 0, insert_mode)
         init_cost = ops.tour_cost(init, Dc)                                # test.py:90
         gt = torch.stack([R if g == "regret_pred" else Dc for g in guides]).contiguous()
+        Ds = Dc
+        if starts > 1:
+            # job c * starts + r = run r of instance c: the matrices are replicated per run, the start tours interleaved
+            init = torch.cat([init[:, None], sampled[b0:b0 + chunk]], dim=1).reshape(-1, n + 1).contiguous()
+            Ds = Dc.repeat_interleave(starts, dim=0)
+            gt = gt.repeat_interleave(starts, dim=1)
+            init_cost = ops.tour_cost(init, Ds)
         torch.cuda.synchronize()
         t2 = time.time()
-        remaining = max(round_limit - (t2 - t0), 0.0)
-        run = lambda: ops.gls_run(Dc, gt, init, init_cost, perturbation_moves=perturbation_moves,   # noqa: E731
+        remaining = max(round_limit - (t2 - t0) - sample_s / n_rounds, 0.0)
+        run = lambda: ops.gls_run(Ds, gt, init, init_cost, perturbation_moves=perturbation_moves,   # noqa: E731
                                   first_improvement=first_improvement, max_outer_iters=max_outer_iters,
                                   time_limit_s=remaining, trace_cap=trace_cap, want_trace_time=want_trace_time, imp_cap=imp_cap)
         executed = None
         if count_executed:
-            with ops.executed_evals(Dc.shape[0]) as x:
+            with ops.executed_evals(Ds.shape[0]) as x:
                 r = run()
             executed = x.counts
-            timing["cycle_records"] = [x.record(Dc.shape[0], k).clone() for k in range(1, ops.EXEC_RECORDS)]     # of the last device load
+            timing["cycle_records"] = [x.record(Ds.shape[0], k).clone() for k in range(1, ops.EXEC_RECORDS)]     # of the last device load
         else:
             r = run()
         torch.cuda.synchronize()
@@ -185,6 +217,16 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
         timing["init_s"] += t2 - t1
         timing["search_s"] += t3 - t2
         timing["chunks"] += 1
+        start_costs = best_start = None
+        if starts > 1:
+            start_costs = r.best_cost.reshape(-1, starts).clone()
+            best_start = ops.first_argmin(start_costs)
+            win = torch.arange(Dc.shape[0], device=D.device) * starts + best_start
+            r = dataclasses.replace(r, **{f.name: getattr(r, f.name)[win] for f in dataclasses.fields(r)
+                                          if getattr(r, f.name) is not None})
+            init_cost = init_cost[win]
+            if executed is not None:
+                executed = executed[win]
         lb = None
         if lower_bound:
             lb = ops.one_tree_bound(Dc, r.best_cost, max_iters=bound_iters, want_pi=False)
@@ -192,7 +234,7 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
             timing["bound_s"] = timing.get("bound_s", 0.0) + (time.time() - t3)
         outs.append((r, init_cost, R if keep_regret else None,
                      torch.full((Dc.shape[0],), t0, dtype=torch.float64), torch.full((Dc.shape[0],), t2, dtype=torch.float64),
-                     executed, lb))
+                     executed, lb, start_costs, best_start))
     cat = lambda xs: torch.cat(xs) if len(xs) > 1 else xs[0]  # noqa: E731
     return SolveResult(
         best_tour=cat([o[0].best_tour for o in outs]), best_cost=cat([o[0].best_cost for o in outs]),
@@ -209,7 +251,9 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
         evals_executed=cat([o[5] for o in outs]) if count_executed else None,
         start_time=cat([o[3] for o in outs]), launch_time=cat([o[4] for o in outs]),
         lower_bound=cat([o[6].bound for o in outs]) if lower_bound else None,
-        bound_exit=cat([o[6].exit_kind for o in outs]) if lower_bound else None)
+        bound_exit=cat([o[6].exit_kind for o in outs]) if lower_bound else None,
+        start_costs=cat([o[7] for o in outs]) if starts > 1 else None,
+        best_start=cat([o[8] for o in outs]) if starts > 1 else None)
 
 
 def synthetic_model(seed=1234, device="cuda"):

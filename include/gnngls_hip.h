@@ -48,6 +48,9 @@ extern "C" {
                                          see there); that edge keeps its earlier label */
 #define GNNGLS_STATUS_BAD_ORDER 5     /* gnngls_insertion, GNNGLS_INSERT_GIVEN_ORDER: the instance's row of `order` is not a
                                          permutation of the non-depot nodes; its tour row was left untouched */
+#define GNNGLS_SAMPLE_BAD_WEIGHTS 6   /* gnngls_sample_nn_tours: a step of the walk met weights np.random.choice refuses (a NaN,
+                                         negative or infinite probability, or a total that is not finite and positive); the
+                                         walk's tour row is filled with -1 */
 
 int gnngls_abi_version(void);
 const char *gnngls_last_error(void);
@@ -165,6 +168,35 @@ int gnngls_cheapest_insertion(const int32_t *sub_tour, int len, const int32_t *n
 #define GNNGLS_BOUND_EXIT_TOUR 2      /* the minimum 1-tree is a tour: the bound is the optimum */
 int gnngls_one_tree_bound(const double *D, const double *ub, int B, int n, int max_iters, double *bound, double *pi, int32_t *iters,
                           int32_t *exit_kind, int32_t *status, void *stream);
+
+/* ---- sampled nearest-neighbour walks (algorithms.py:21-50: probabilistic_nearest_neighbour) ----------------------------------
+ * R independent walks per instance, one wavefront each, one launch for the B * R walks.  Walk (b, r):
+ *   tour = [depot]; at every step i = tour[-1] and the candidates are the unvisited nodes j in ascending id, g_j = W[b,i,j];
+ *   p = g; if any g_j is +-inf then p_j = 1.0 where g_j is infinite and 0.0 elsewhere (:34-36); if the sum of p is 0 then every
+ *   p_j = 1.0 (:39-40); if `invert` then p_j = 1 / p_j (:43-44);
+ *   where the reference's np.random.choice would raise -- some p_j is NaN, negative or infinite, or the total is not finite and
+ *   positive (a zero weight under `invert` is such a case) -- the walk stops: status[b,r] = GNNGLS_SAMPLE_BAD_WEIGHTS and its row
+ *   of `tours` is filled with -1;
+ *   draw: x = u * total; the first candidate with p_j > 0 whose running sum exceeds x, or, if rounding leaves none, the last
+ *   candidate with p_j > 0 (a candidate of weight zero could be the first to exceed x only through rounding: it is never picked).
+ * Summation order (it decides ties at a boundary, so it is part of the definition).  Node j sits on lane j % 64, slot j / 64; a
+ * node that is no candidate contributes +0.0.  For slot s = 0, 1, .. in order: c_s = the inclusive doubling scan of the slot over
+ * its 64 lanes (for d = 1, 2, 4, 8, 16, 32 in order every lane l >= d adds the value lane l - d held before the round);
+ * running sum of node j = base_s + c_s[j % 64] with base_0 = +0.0 and base_{s+1} = base_s + c_s[63]; total = the last base.  The
+ * sum of the all-zero rule is this total on the p before inversion.  Every step is one fp64 operation rounded once.
+ * Uniforms: u[b,r,s] in [0,1) for step s = 0 .. n-2 (the last step draws too, as the reference does) -- the caller's array, or with
+ * u == NULL the 53-bit uniform ((o0 << 32 | o1) >> 11) * 2^-53 of Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and
+ * counter (b, r, s, 0), (o0, o1) its first two output words.  A walk therefore depends on its instance's matrix and its own
+ * uniforms only, never on the launch shape or on its neighbours.  The draws are NOT NumPy's: given `u` the walk is pinned bit for
+ * bit (tests/test_sampling_cpu.py restates it in NumPy), against the reference it is pinned in law.
+ *   W [B,n,n] fp64 (read as indexed: W[b,i,j] with i the current node); tours [B,R,n+1] int32 closed tours from `depot`;
+ *   status [B,R] int32 0 or GNNGLS_SAMPLE_BAD_WEIGHTS.  A u outside [0,1) still yields a closed permutation (which: unspecified).
+ * 3 <= n <= GNNGLS_SAMPLE_MAX_N (visited bits and candidate weights stay in registers, 16 nodes per lane at most; a larger n
+ * returns GNNGLS_ERR_UNSUPPORTED), R >= 1, B * R < 2^31.  Bad arguments are rejected on the host before any device work; B == 0
+ * returns GNNGLS_OK. */
+#define GNNGLS_SAMPLE_MAX_N 1024
+int gnngls_sample_nn_tours(const double *W, int B, int n, int R, int depot, int invert, uint64_t seed, const double *u,
+                           int32_t *tours, int32_t *status, void *stream);
 
 /* Host-side query (oracle/one_tree.c has no counterpart; scripts/bench_bounds.py reports it): the launch gnngls_one_tree_bound makes
  * for n nodes -- *threads workgroup size (64 = one wavefront per instance, n <= 256), *lds_bytes dynamic LDS per workgroup,

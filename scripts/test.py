@@ -10,6 +10,9 @@ constructors (algorithms.py:82-108) instead, `--init_weight weight` builds the s
 `--lower_bound` adds the columns `lower_bound` -- the Held-Karp 1-tree bound of the instance (gnngls_amd.ops.one_tree_bound, computed
 after the search with ub = the returned cost: lower_bound <= optimum <= best_cost, certified) -- and `gap_bound` =
 (best_cost / lower_bound - 1) * 100, the gap that needs no stored optimum; without the flag the pickle has the seven columns above.
+`--starts R` searches every instance R times within the same --time_limit (run 0 from the start tour, the others from sampled
+nearest-neighbour walks keyed by `--start_seed`; a batch then holds device capacity / R instances) and records the run that ended
+cheapest; the pickle's columns are unchanged.
 
 Search progress (test.py:97-117).  The reference appends one row per accepted move; a 10 s TSP100 search on the GPU
 accepts ~2e6 moves per instance, i.e. ~20 GB of rows for a 1024-instance batch.  The default record here is therefore
@@ -74,6 +77,10 @@ def parse_args():
     parser.add_argument('--lower_bound', action='store_true',
                         help='also compute the Held-Karp 1-tree lower bound of every instance on the GPU (after its search, outside '
                              'the budget) and write the columns lower_bound and gap_bound = (best_cost / lower_bound - 1) * 100')
+    parser.add_argument('--starts', type=int, default=1, metavar='R',
+                        help='search every instance R times concurrently (run 0 from --init_tour, runs 1..R-1 from sampled '
+                             'nearest-neighbour walks on the distances) and keep the cheapest run; a batch holds capacity / R instances')
+    parser.add_argument('--start_seed', type=int, default=0, metavar='S', help='seed of the sampled start tours of --starts')
     return parser.parse_args()
 
 
@@ -142,7 +149,8 @@ def solve_block(names, test_set, model, scalers, args, chunk, budget='per_instan
                                perturbation_moves=args.perturbation_moves, trace_cap=args.full_trace,
                                want_trace_time=args.full_trace > 0, chunk=chunk, budget=budget, imp_cap=IMP_CAP,
                                features=features, init=getattr(args, 'init_tour', 'nearest_neighbor'),
-                               init_weight=getattr(args, 'init_weight', 'auto'), lower_bound=want_bound)
+                               init_weight=getattr(args, 'init_weight', 'auto'), lower_bound=want_bound,
+                               starts=getattr(args, 'starts', 1), start_seed=getattr(args, 'start_seed', 0))
     bounds = res.lower_bound.cpu().numpy() if want_bound else None
     res.imp_cost, res.imp_time, res.imp_len = res.imp_cost.cpu(), res.imp_time.cpu(), res.imp_len.cpu()
     res.moves = res.moves.cpu()
@@ -242,7 +250,7 @@ def main():
     test_set = datasets.TSPDataset(args.data_path, feat_drop_idx=params.get('efeat_drop_idx', []))
     model, scalers = load_model(args, params, test_set)
 
-    chunk = args.batch_size or max(ops.gls_resident_capacity(test_set.G.n), 1)
+    chunk = args.batch_size or max(ops.gls_resident_capacity(test_set.G.n) // max(args.starts, 1), 1)
     lo, hi = parallel.shard_range(len(test_set.instances), world, rank)       # this rank's block of instances
     mine = test_set.instances[lo:hi]
     records, gaps, bound_gaps = [], [], []
