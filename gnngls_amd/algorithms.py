@@ -1,6 +1,7 @@
 """Mirror of gnngls/algorithms.py (reference algorithms.py:9-195): `nearest_neighbor`, `cheapest_insertion`,
 `insertion`, `local_search`, `guided_local_search` with the reference's signatures, return values and side
 effects, executed by the HIP kernels (the persistent search kernel, the one-launch insertion constructor).
+`alpha_nearness` (no counterpart in the reference) writes a model-free guide attribute for guided_local_search.
 
 The probabilistic constructors (algorithms.py:21-64: `probabilistic_nearest_neighbour`, `best_probabilistic_nearest_neighbour`)
 have the reference's signatures plus a trailing `seed` and the reference's LAW, not its draws: np.random.choice draws from NumPy's
@@ -94,6 +95,20 @@ def best_probabilistic_nearest_neighbour(G, depot, n_iters, guide='weight', weig
     W = ops.as_dev(_attr_matrix(G, guide)[None], torch.float64)
     D = W if weight == guide else ops.as_dev(_attr_matrix(G, weight)[None], torch.float64)
     return ops.best_sampled_tour(W, D, int(n_iters), depot, True, seed)[0][0].tolist()
+
+
+def alpha_nearness(G, weight="weight", attr="alpha", max_iters=2000):
+    """Writes Helsgaun's alpha-nearness of every edge of G as the edge attribute `attr` (the reference has no counterpart; it is
+    the classical relaxation of the regret its model predicts) and returns G: guided_local_search(G, ..., guides=["alpha"]) then
+    runs as it does on any other guide.  The potentials come from the Held-Karp ascent of ops.one_tree_bound on `weight` with at
+    most `max_iters` 1-trees and ub = the nearest-neighbour tour's length (max_iters=0: zero potentials)."""
+    D = ops.as_dev(_attr_matrix(G, weight)[None], torch.float64)
+    pi = None
+    if max_iters > 0:
+        pi = ops.one_tree_bound(D, ops.tour_cost(ops.nearest_neighbor(D), D), max_iters=int(max_iters)).pi
+    A = ops.alpha_nearness(D, pi)[0].cpu().numpy()
+    nx.set_edge_attributes(G, {(u, v): float(A[u, v]) for u, v in G.edges}, attr)
+    return G
 
 
 def _check_status(r, what):

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/gnngls_hip.h"
+#include "alpha_kernels.h"
 #include "bounds_kernels.h"
 #include "constructors_kernels.h"
 #include "gls_kernels.h"
@@ -265,6 +266,20 @@ int gnngls_one_tree_bound_describe(int n, int *threads, int *lds_bytes, int *nod
     if (lds_bytes) *lds_bytes = gnngls::one_tree_lds_bytes(n);
     if (nodes_per_lane) *nodes_per_lane = t > 64 ? 4 : (n + 63) / 64;
     return GNNGLS_OK;
+}
+
+static_assert(GNNGLS_ALPHA_MAX_N == gnngls::kAlphaMaxN && GNNGLS_STATUS_ASYMMETRIC == gnngls::kAlphaStatusAsymmetric,
+              "include/gnngls_hip.h and alpha_kernels.h disagree");
+
+int gnngls_alpha_nearness(const double *D, const double *pi, int B, int n, double *alpha, int32_t *status, void *stream) {
+    if (B < 1) return fail(GNNGLS_ERR_ARG, "alpha_nearness: B=%d must be >= 1", B);
+    if (n < 3) return fail(GNNGLS_ERR_ARG, "alpha_nearness: n=%d must be >= 3", n);
+    if (n > GNNGLS_ALPHA_MAX_N)
+        return fail(GNNGLS_ERR_UNSUPPORTED, "alpha_nearness: n=%d exceeds the largest supported instance (n <= %d: the Prim state of an "
+                    "instance lives in the registers of one workgroup)", n, GNNGLS_ALPHA_MAX_N);
+    if (!D || !alpha || !status) return fail(GNNGLS_ERR_ARG, "alpha_nearness: NULL pointer (D, alpha, status)");
+    hipError_t e = gnngls::launch_alpha_nearness(D, pi, B, n, alpha, status, (hipStream_t)stream);
+    return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "alpha_nearness");
 }
 
 static_assert(GNNGLS_SAMPLE_MAX_N == gnngls::kSampleMaxN && GNNGLS_SAMPLE_BAD_WEIGHTS == GNNGLS_SAMPLE_BAD_WEIGHTS_DEV,

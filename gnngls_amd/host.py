@@ -58,6 +58,47 @@ def lower_bound(G, tour=None, weight="weight", max_iters=2000):
     return float(ops.one_tree_bound(D, ub, max_iters=max_iters, want_pi=False).bound[0])
 
 
+def alpha_nearness(D, pi=None):
+    """Helsgaun's alpha-nearness of one instance in NumPy fp64: the definition of include/gnngls_hip.h restated, O(n^2), the
+    reference gnngls_amd.ops.alpha_nearness is compared against bit for bit (the reference package has no counterpart).
+    D [n,n] symmetric, pi [n] or None (zeros) -> alpha [n,n].  Canonical weight w(i,j) = ((D[i][j] + pi[min(i,j)]) +
+    pi[max(i,j)]) + 0.0; for 1 <= i < j beta(i,j) = the largest w on the path between i and j in a minimum spanning tree of
+    nodes 1..n-1 (Prim: when u enters with parent p and key k, beta(u,v) = max(beta(p,v), k) for every in-tree v, beta(u,p) = k)
+    and alpha = w - beta; alpha(0,j) = w(0,j) - (second smallest w(0,.)), floored at +0.0; +0.0 on the diagonal.  Every beta is
+    one of the w, so the result does not depend on Prim's tie-breaks."""
+    import numpy as np
+    D = np.asarray(D, dtype=np.float64)
+    n = D.shape[0]
+    assert D.shape == (n, n) and n >= 3
+    pi = np.zeros(n) if pi is None else np.asarray(pi, dtype=np.float64)
+    idx = np.arange(n)
+    w = ((D + pi[np.minimum.outer(idx, idx)]) + pi[np.maximum.outer(idx, idx)]) + 0.0
+    beta = np.zeros((n, n))
+    key = np.full(n, np.inf)
+    parent = np.full(n, -1)
+    outside = idx >= 1                                    # node 0 never takes part in Prim
+    u = 1
+    for step in range(1, n):
+        if step > 1:
+            u = int(np.argmin(np.where(outside, key, np.inf)))
+            p, k = int(parent[u]), key[u]
+            tree = ~outside
+            tree[0] = False
+            b = np.maximum(beta[p, tree], k)
+            beta[u, tree] = b
+            beta[tree, u] = b
+            beta[u, p] = beta[p, u] = k
+        outside[u] = False
+        lower = outside & (w[u] < key)
+        key[lower] = w[u, lower]
+        parent[lower] = u
+    alpha = w - beta
+    a0 = w[0, 1:] - np.partition(w[0, 1:], 1)[1]
+    alpha[0, 1:] = alpha[1:, 0] = np.where(a0 > 0, a0, 0.0)
+    alpha[idx, idx] = 0.0
+    return alpha
+
+
 def fixed_edge_tour(G, e, scale=None, lkh_path=None, base_tour=None, label_iters=None, perturbation_moves=None, **kwargs):
     """A tour of G that holds edge e (reference __init__.py:63-79: LKH with e fixed).  Here: the fixed-edge search of
     gnngls_amd.labels on the device -- guided_local_search on G's weights with e's weight lowered by M, guide = those weights,

@@ -289,6 +289,34 @@ def one_tree_describe(n):
             "form": f"{t // 64} wavefront(s) per instance, {slots} node(s) per lane in registers, matrix rows from global memory"}
 
 
+ALPHA_MAX_N = 1024                                            # GNNGLS_ALPHA_MAX_N
+
+
+def alpha_nearness(D, pi=None):
+    """Helsgaun's alpha-nearness of every edge of a batch, one launch: alpha(e) = (minimum 1-tree forced through e) - (minimum
+    1-tree) under the potentials pi (include/gnngls_hip.h states the definition; host.alpha_nearness restates it in NumPy, bit
+    for bit).  D [B,n,n] fp64 bitwise symmetric, pi [B,n] fp64 (one_tree_bound(...).pi) or None (all zeros) -> alpha [B,n,n]
+    fp64, symmetric, >= 0, +0.0 on the diagonal and on the edges of the minimum 1-tree: a guide matrix for gls_run.  A matrix
+    that is not symmetric raises."""
+    B, n, n2 = D.shape
+    assert n == n2 and D.dtype == torch.float64
+    if pi is not None:
+        assert pi.dtype == torch.float64 and pi.shape == (B, n), f"pi shape {tuple(pi.shape)} is not [{B},{n}]"
+        pi = pi.to(D.device).contiguous()
+    out = torch.empty((B, n, n), dtype=torch.float64, device=D.device)
+    status = torch.zeros((B,), dtype=torch.int32, device=D.device)
+    L = _lib.load()
+    if not hasattr(L, "gnngls_alpha_nearness"):
+        raise _lib.GnnglsHipError("this build of libgnngls_hip.so has no gnngls_alpha_nearness")
+    _lib.check(L.gnngls_alpha_nearness(_lib.ptr(D.contiguous()), _lib.ptr(pi), B, n, _lib.ptr(out), _lib.ptr(status),
+                                       _lib.current_stream()), "alpha_nearness")
+    bad = (status == STATUS_ASYMMETRIC).nonzero().flatten().tolist()
+    if bad:
+        raise ValueError(f"alpha_nearness: the matrices of instances {bad[:8]} are not bitwise symmetric (status {STATUS_ASYMMETRIC}): "
+                         "alpha-nearness is defined for symmetric costs only")
+    return out
+
+
 def gls_run(D, guides, init_tour, init_cost, perturbation_moves=30, first_improvement=False,
             max_outer_iters=-1, time_limit_s=0.0, watchdog_s=None, trace_cap=0, want_trace_time=False,
             want_penalty=False, penalty_bits=0, retry_overflow=True, imp_cap=0, retry_asymmetric=True):

@@ -107,7 +107,8 @@ def predict_regret(model, D, scalers, features=None):
 def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit=10.0, perturbation_moves=20,
                 first_improvement=False, max_outer_iters=-1, trace_cap=0, want_trace_time=False, chunk=None,
                 keep_regret=False, budget="per_instance", imp_cap=0, features=None, count_executed=False,
-                init="nearest_neighbor", init_weight="auto", lower_bound=False, bound_iters=2000, starts=1, start_seed=0):
+                init="nearest_neighbor", init_weight="auto", lower_bound=False, bound_iters=2000, starts=1, start_seed=0,
+                alpha_iters=2000):
     """D [B,n,n] fp64 CUDA tensor (symmetric).  Returns SolveResult with per-instance tensors.
 
     budget="per_instance" (default, the reference's meaning of --time_limit, test.py:64,92): every instance is searched
@@ -125,7 +126,15 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
     starts: R > 1 searches every instance R times in one launch (run 0 from `init`, runs 1..R-1 from sampled walks on D keyed by
     `start_seed` and the instance's index in the batch, so chunking does not change them) and returns the first run with the
     smallest cost; a chunk holds capacity // R instances.  SolveResult.start_costs [B,R], .best_start [B], timing["sample_s"]
-    (the one sampling launch of the batch; its time is taken off the rounds' budgets in equal shares)."""
+    (the one sampling launch of the batch; its time is taken off the rounds' budgets in equal shares).
+    guides: any mix and order of 'regret_pred' (the model), 'weight' (the distances) and 'alpha' -- Helsgaun's alpha-nearness
+    (ops.alpha_nearness), computed per chunk inside its budget like the forward: the Held-Karp ascent of ops.one_tree_bound with
+    ub = the nearest-neighbour tour's length on the distances and at most `alpha_iters` 1-trees gives the potentials
+    (alpha_iters=0: no ascent, zero potentials), one more launch the matrix; its time goes to timing["alpha_s"] (absent when the
+    guide is unused).  It needs no model.  The start tour keeps the reference's rule whatever 'alpha' does: alpha is zero on the n
+    edges of the minimum 1-tree of every instance and is no matrix to walk greedily.  alpha_iters defaults to bound_iters'
+    default, the oracle's 2000: measured (profiles/alpha_guide.json) it gives the best alpha guide wherever the budget is three
+    times the ascent's time or more (0.13 s for 1,024 TSP100, 0.35 s for 256 TSP200 instances); under a shorter budget lower it."""
     if init not in INIT_TOURS:
         raise ValueError(f"unknown start tour {init!r} (one of {', '.join(INIT_TOURS)})")
     if init_weight not in ("auto", "weight"):
@@ -140,10 +149,14 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
     B, n, _ = D.shape
     guides = list(guides)
     need_model = "regret_pred" in guides
+    need_alpha = "alpha" in guides
+    alpha_iters = int(alpha_iters)
+    if need_alpha and alpha_iters < 0:
+        raise ValueError(f"alpha_iters={alpha_iters} must be >= 0")
     if need_model and (model is None or scalers is None):
         raise ValueError("guide 'regret_pred' needs a model and scalers")
     for g in guides:
-        if g not in ("regret_pred", "weight"):
+        if g not in ("regret_pred", "weight", "alpha"):
             raise ValueError(f"unknown guide {g!r}")
     if B == 0:                            # an empty shard (more ranks than instances): nothing to launch
         e64 = torch.zeros((0,), dtype=torch.float64, device=D.device)
@@ -179,13 +192,23 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
             R = predict_regret(model, Dc, scalers, None if features is None else features[b0:b0 + chunk])
             torch.cuda.synchronize()
         t1 = time.time()
+        A = None
+        if need_alpha:
+            pi = None
+            if alpha_iters > 0:
+                ub = ops.tour_cost(ops.nearest_neighbor(Dc), Dc)
+                pi = ops.one_tree_bound(Dc, ub, max_iters=alpha_iters).pi
+            A = ops.alpha_nearness(Dc, pi)
+            torch.cuda.synchronize()
+            timing["alpha_s"] = timing.get("alpha_s", 0.0) + (time.time() - t1)
+        t1a = time.time()
         # test.py:70-88: the start tour is greedy on 'regret_pred' whenever that guide is used AT ALL (not only when it
         # comes first), otherwise on 'weight'
         Wi = R if (need_model and init_weight == "auto") else Dc
         # the defaults give nearest_neighbor(R if need_model else Dc): the call this function always made
         init = ops.nearest_neighbor(Wi) if insert_mode is None else ops.insertion(Wi, 0, insert_mode)
         init_cost = ops.tour_cost(init, Dc)                                # test.py:90
-        gt = torch.stack([R if g == "regret_pred" else Dc for g in guides]).contiguous()
+        gt = torch.stack([{"regret_pred": R, "weight": Dc, "alpha": A}[g] for g in guides]).contiguous()
         Ds = Dc
         if starts > 1:
             # job c * starts + r = run r of instance c: the matrices are replicated per run, the start tours interleaved
@@ -214,7 +237,7 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
             warnings.warn(f"solve_batch: the device watchdog stopped {aborted} search(es) early (best-so-far returned)",
                           RuntimeWarning, stacklevel=2)
         timing["forward_s"] += t1 - t0
-        timing["init_s"] += t2 - t1
+        timing["init_s"] += t2 - t1a
         timing["search_s"] += t3 - t2
         timing["chunks"] += 1
         start_costs = best_start = None

@@ -1,6 +1,6 @@
 """PyTorch-ROCm custom operators of the hot path: `torch.ops.gnngls.*` (north_star).
 
-Nine operators are registered with `torch.library` over the C ABI of libgnngls_hip.so (include/gnngls_hip.h).  Each has
+Ten operators are registered with `torch.library` over the C ABI of libgnngls_hip.so (include/gnngls_hip.h).  Each has
 exactly ONE implementation, for the CUDA dispatch key (= HIP on ROCm): there is no CPU kernel behind any of them, so
 calling one with CPU tensors fails in the dispatcher ("no CPU fallback" is structural, not a runtime check).  Shape
 functions (fake/meta kernels) are registered so the ops can be traced and used under FakeTensorMode.  All ops enqueue on
@@ -20,6 +20,8 @@ the current HIP stream, take caller-owned contiguous tensors and retain nothing.
     cheapest_insertion(sub_tour[B,len] i32, node[B] i32, W) -> (tour[B,len+1] i32, cost[B] f64)   algorithms.py:67-79
     one_tree_bound(D[B,n,n] f64, ub[B] f64, max_iters) -> (bound[B] f64, pi[B,n] f64, iters[B] i32, exit_kind[B] i32, status[B] i32)
         the Held-Karp 1-tree lower bound of oracle/one_tree.c (in place of Concorde's optimum, scripts/test.py:62,104)
+    alpha_nearness(D[B,n,n] f64, pi[B,n] f64 or None) -> alpha[B,n,n] f64
+        Helsgaun's alpha-nearness under the potentials of one_tree_bound (None: zeros): a model-free guide for gls_run
     sample_nn_tours(W[B,n,n] f64, R, depot, invert, seed, u[B,R,n-1] f64 or None) -> (tours[B,R,n+1] i32, status[B,R] i32)
         algorithms.py:21-50, R sampled walks per instance; status 6 (and a tour of -1) marks a walk that met weights which are
         no probabilities -- the op reports, gnngls_amd.ops.sample_nn_tours raises
@@ -41,6 +43,7 @@ _LIB.define("gls_run(Tensor D, Tensor guides, Tensor init_tour, Tensor init_cost
 _LIB.define("insertion(Tensor W, int depot, str mode, Tensor? order) -> Tensor")
 _LIB.define("cheapest_insertion(Tensor sub_tour, Tensor node, Tensor W) -> (Tensor, Tensor)")
 _LIB.define("one_tree_bound(Tensor D, Tensor ub, int max_iters) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
+_LIB.define("alpha_nearness(Tensor D, Tensor? pi) -> Tensor")
 _LIB.define("sample_nn_tours(Tensor W, int R, int depot, bool invert, int seed, Tensor? u) -> (Tensor, Tensor)")
 
 _workspaces = {}      # device index -> uint8 scratch tensor for the forward (grown on demand, reused across calls)
@@ -107,6 +110,7 @@ _LIB.impl("gls_run", _gls_run, "CUDA")
 _LIB.impl("insertion", ops.insertion, "CUDA")
 _LIB.impl("cheapest_insertion", ops.cheapest_insertion, "CUDA")
 _LIB.impl("one_tree_bound", _one_tree_bound, "CUDA")
+_LIB.impl("alpha_nearness", ops.alpha_nearness, "CUDA")
 _LIB.impl("sample_nn_tours", ops.sample_nn_launch, "CUDA")
 
 
@@ -154,6 +158,11 @@ def _(D, ub, max_iters):
     B, n = D.shape[0], D.shape[1]
     i32 = lambda: D.new_empty((B,), dtype=torch.int32)  # noqa: E731
     return D.new_empty((B,), dtype=torch.float64), D.new_empty((B, n), dtype=torch.float64), i32(), i32(), i32()
+
+
+@torch.library.register_fake("gnngls::alpha_nearness")
+def _(D, pi):
+    return D.new_empty(tuple(D.shape), dtype=torch.float64)
 
 
 @torch.library.register_fake("gnngls::sample_nn_tours")

@@ -169,6 +169,31 @@ int gnngls_cheapest_insertion(const int32_t *sub_tour, int len, const int32_t *n
 int gnngls_one_tree_bound(const double *D, const double *ub, int B, int n, int max_iters, double *bound, double *pi, int32_t *iters,
                           int32_t *exit_kind, int32_t *status, void *stream);
 
+/* ---- alpha-nearness (Helsgaun): a model-free, regret-like search guide from the 1-tree -----------------------------------------
+ * alpha(e) = (cost of the minimum 1-tree forced through e) - (cost of the minimum 1-tree) under node potentials pi, the
+ * classical relaxation of the regret the model predicts ((best tour through e - optimum) / optimum).  With the pi of
+ * gnngls_one_tree_bound it is the guide a search takes in place of a model's prediction.  Definition (the contract):
+ *   D [B,n,n] fp64 bitwise symmetric, pi [B,n] fp64 or NULL (all zeros), 3 <= n <= GNNGLS_ALPHA_MAX_N; node 0 is the special
+ *   node, as in gnngls_one_tree_bound and oracle/one_tree.c; every operation below is one fp64 operation rounded once.
+ *   Canonical weight: w(i,j) = ((D[i][j] + pi[min(i,j)]) + pi[max(i,j)]) + 0.0 -- the potential of the smaller node first, so
+ *   that w(i,j) == w(j,i) bit for bit (the bound's (row + pi[u]) + pi[v] depends on which endpoint entered the tree first;
+ *   alpha must not); the last term only reads a weight of -0.0 as +0.0.
+ *   Pairs 1 <= i < j: beta(i,j) = the largest w on the path between i and j in a minimum spanning tree of nodes 1..n-1 under w
+ *   -- the minimax-path value, the same for every minimum spanning tree -- and alpha(i,j) = w(i,j) - beta(i,j).
+ *   Pairs with node 0: m2 = the second smallest of w(0,j), j = 1..n-1, counted with multiplicity;
+ *   alpha(0,j) = w(0,j) - m2 if that is > 0, else +0.0.
+ *   alpha [B,n,n] fp64 is bitwise symmetric with a +0.0 diagonal.
+ * Every beta is one of the w, selected by comparisons and never computed: alpha is bit-determined by (D, pi) and does not depend
+ * on the tie-breaks inside Prim; it is >= 0, and on an instance without ties exactly n unordered pairs -- the edges of the
+ * minimum 1-tree -- have alpha = +0.0.  gnngls_amd.host.alpha_nearness restates the definition in NumPy.
+ *   status [B]: 0, or GNNGLS_STATUS_ASYMMETRIC for an instance whose matrix is not bitwise symmetric (one pass in front of Prim);
+ *   that instance's alpha is filled with NaN.  Non-finite costs or potentials: unspecified values, every index stays in range.
+ * One workgroup per instance, one launch for the batch, O(n^2) work per instance (ONE spanning tree, where the ascent of
+ * gnngls_one_tree_bound builds up to max_iters).  Bad arguments -- a NULL D, alpha or status, B < 1, n < 3 (GNNGLS_ERR_ARG),
+ * n > GNNGLS_ALPHA_MAX_N (GNNGLS_ERR_UNSUPPORTED) -- are rejected on the host before any device work. */
+#define GNNGLS_ALPHA_MAX_N 1024
+int gnngls_alpha_nearness(const double *D, const double *pi, int B, int n, double *alpha, int32_t *status, void *stream);
+
 /* ---- sampled nearest-neighbour walks (algorithms.py:21-50: probabilistic_nearest_neighbour) ----------------------------------
  * R independent walks per instance, one wavefront each, one launch for the B * R walks.  Walk (b, r):
  *   tour = [depot]; at every step i = tour[-1] and the candidates are the unvisited nodes j in ascending id, g_j = W[b,i,j];

@@ -13,6 +13,8 @@ after the search with ub = the returned cost: lower_bound <= optimum <= best_cos
 `--starts R` searches every instance R times within the same --time_limit (run 0 from the start tour, the others from sampled
 nearest-neighbour walks keyed by `--start_seed`; a batch then holds device capacity / R instances) and records the run that ended
 cheapest; the pickle's columns are unchanged.
+The guide `alpha` (alone or mixed with the others, e.g. `alpha weight`) is Helsgaun's alpha-nearness under the potentials of the
+Held-Karp ascent, computed on the GPU inside the budget (`--alpha_iters`, gnngls_amd.ops.alpha_nearness): it needs no checkpoint.
 
 Search progress (test.py:97-117).  The reference appends one row per accepted move; a 10 s TSP100 search on the GPU
 accepts ~2e6 moves per instance, i.e. ~20 GB of rows for a 1024-instance batch.  The default record here is therefore
@@ -81,6 +83,9 @@ def parse_args():
                         help='search every instance R times concurrently (run 0 from --init_tour, runs 1..R-1 from sampled '
                              'nearest-neighbour walks on the distances) and keep the cheapest run; a batch holds capacity / R instances')
     parser.add_argument('--start_seed', type=int, default=0, metavar='S', help='seed of the sampled start tours of --starts')
+    parser.add_argument('--alpha_iters', type=int, default=2000, metavar='K',
+                        help="guide 'alpha' (Helsgaun's alpha-nearness, no model needed): the largest number of 1-trees of the "
+                             'Held-Karp ascent that gives its potentials, inside the budget (0 = no ascent, zero potentials)')
     return parser.parse_args()
 
 
@@ -150,7 +155,8 @@ def solve_block(names, test_set, model, scalers, args, chunk, budget='per_instan
                                want_trace_time=args.full_trace > 0, chunk=chunk, budget=budget, imp_cap=IMP_CAP,
                                features=features, init=getattr(args, 'init_tour', 'nearest_neighbor'),
                                init_weight=getattr(args, 'init_weight', 'auto'), lower_bound=want_bound,
-                               starts=getattr(args, 'starts', 1), start_seed=getattr(args, 'start_seed', 0))
+                               starts=getattr(args, 'starts', 1), start_seed=getattr(args, 'start_seed', 0),
+                               alpha_iters=getattr(args, 'alpha_iters', 2000))
     bounds = res.lower_bound.cpu().numpy() if want_bound else None
     res.imp_cost, res.imp_time, res.imp_len = res.imp_cost.cpu(), res.imp_time.cpu(), res.imp_len.cpu()
     res.moves = res.moves.cpu()
