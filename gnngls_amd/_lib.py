@@ -34,6 +34,8 @@ SIGNATURES = {
     "gnngls_one_tree_bound": [_vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],
     "gnngls_one_tree_bound_describe": [_int, _vp, _vp, _vp],
     "gnngls_alpha_nearness": [_vp, _vp, _int, _int, _vp, _vp, _vp],
+    "gnngls_or_opt_best_move": [_vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp],
+    "gnngls_or_opt_descent": [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp],
     "gnngls_sample_nn_tours": [_vp, _int, _int, _int, _int, _int, _u64, _vp, _vp, _vp, _vp],
     "gnngls_gls_run": [_vp, _vp, _int, _int, _int, _vp, _vp, _int, _int, _int, _i64, _f64, _f64,
                        _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp],
@@ -110,6 +112,8 @@ _BOUNDS = ("gnngls_one_tree_bound", "gnngls_one_tree_bound_describe")
 _SAMPLING = ("gnngls_sample_nn_tours",)
 # alpha-nearness (an older build named by GNNGLS_HIP_SO lacks it; ops.alpha_nearness then raises)
 _ALPHA = ("gnngls_alpha_nearness",)
+# Or-opt (an older build named by GNNGLS_HIP_SO lacks it; ops.or_opt_best_move / or_opt_descent then raise)
+_OR_OPT = ("gnngls_or_opt_best_move", "gnngls_or_opt_descent")
 _lib = None
 
 
@@ -132,7 +136,7 @@ def load():
         import torch  # noqa: F401
         L = ctypes.CDLL(SO)
         for name, argtypes in SIGNATURES.items():
-            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS or name in _BOUNDS or name in _SAMPLING or name in _ALPHA) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
+            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS or name in _BOUNDS or name in _SAMPLING or name in _ALPHA or name in _OR_OPT) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
                 continue              # an older build of the library named by GNNGLS_HIP_SO (same-box A/B of kernel variants)
             f = getattr(L, name)      # AttributeError if the symbol is missing
             f.argtypes = argtypes

@@ -1,7 +1,8 @@
 """Mirror of gnngls/algorithms.py (reference algorithms.py:9-195): `nearest_neighbor`, `cheapest_insertion`,
 `insertion`, `local_search`, `guided_local_search` with the reference's signatures, return values and side
 effects, executed by the HIP kernels (the persistent search kernel, the one-launch insertion constructor).
-`alpha_nearness` (no counterpart in the reference) writes a model-free guide attribute for guided_local_search.
+`alpha_nearness` (no counterpart in the reference) writes a model-free guide attribute for guided_local_search;
+`or_opt_descent` (no counterpart either) is local_search with Or-opt in relocate's place.
 
 The probabilistic constructors (algorithms.py:21-64: `probabilistic_nearest_neighbour`, `best_probabilistic_nearest_neighbour`)
 have the reference's signatures plus a trailing `seed` and the reference's LAW, not its draws: np.random.choice draws from NumPy's
@@ -153,6 +154,16 @@ def local_search(init_tour, init_cost, D, first_improvement=False):
                     imp_cap=IMP_CAP)
     _check_status(r, "local_search")
     return r.best_tour[0].tolist(), r.best_cost[0].item(), _progress(r, t0)
+
+
+def or_opt_descent(init_tour, init_cost, D, max_seg=3, reverse=True):
+    """local_search above with relocate_a2a replaced by the Or-opt scan (operators.or_opt_a2a: chains of 1..max_seg nodes,
+    reversed too if `reverse`), best improvement, on the GPU (ops.or_opt_descent; no counterpart in the reference)
+    -> (tour, cost, n_moves).  With max_seg=1, reverse=False it returns local_search's tour and cost."""
+    r = ops.or_opt_descent(ops.as_dev(np.asarray(init_tour, dtype=np.int32)[None], torch.int32),
+                           ops.as_dev(np.asarray([init_cost], dtype=np.float64), torch.float64),
+                           ops.as_dev(np.asarray(D, dtype=np.float64)[None], torch.float64), max_seg, reverse)
+    return r.tour[0].tolist(), r.cost[0].item(), int(r.moves[0])
 
 
 def guided_local_search(G, init_tour, init_cost, t_lim, weight="weight", guides=["weight"], perturbation_moves=30,

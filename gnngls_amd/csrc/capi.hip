@@ -21,6 +21,7 @@
 #include "labels_kernels.h"
 #include "model_kernels.h"
 #include "model_plan.h"
+#include "oropt_kernels.h"
 #include "sampling_kernels.h"
 #include "train_kernels.h"
 
@@ -280,6 +281,44 @@ int gnngls_alpha_nearness(const double *D, const double *pi, int B, int n, doubl
     if (!D || !alpha || !status) return fail(GNNGLS_ERR_ARG, "alpha_nearness: NULL pointer (D, alpha, status)");
     hipError_t e = gnngls::launch_alpha_nearness(D, pi, B, n, alpha, status, (hipStream_t)stream);
     return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "alpha_nearness");
+}
+
+static_assert(GNNGLS_OR_OPT_MAX_N == gnngls::kOrOptMaxN && GNNGLS_OR_OPT_MAX_SEG == gnngls::kOrOptMaxSeg &&
+              GNNGLS_STATUS_ASYMMETRIC == gnngls::kOrOptStatusAsymmetric && GNNGLS_STATUS_MOVE_CAP == gnngls::kOrOptStatusMoveCap,
+              "include/gnngls_hip.h and oropt_kernels.h disagree");
+
+// the checks both Or-opt entries share; 0 = the arguments are fine
+static int or_opt_args(const char *what, int B, int n, int max_seg) {
+    if (B < 1) return fail(GNNGLS_ERR_ARG, "%s: B=%d must be >= 1", what, B);
+    if (n < 3) return fail(GNNGLS_ERR_ARG, "%s: n=%d must be >= 3", what, n);
+    if (n > GNNGLS_OR_OPT_MAX_N)
+        return fail(GNNGLS_ERR_UNSUPPORTED, "%s: n=%d exceeds the largest supported instance (n <= %d: a move's selection key holds "
+                    "its positions in ten bits each)", what, n, GNNGLS_OR_OPT_MAX_N);
+    if (max_seg < 1 || max_seg > GNNGLS_OR_OPT_MAX_SEG)
+        return fail(GNNGLS_ERR_ARG, "%s: max_seg=%d must be in 1..%d", what, max_seg, GNNGLS_OR_OPT_MAX_SEG);
+    return GNNGLS_OK;
+}
+
+int gnngls_or_opt_best_move(const int32_t *tour, const double *D, int B, int n, int max_seg, int reverse, double *delta,
+                            int32_t *move, int32_t *new_tour, void *stream) {
+    if (int rc = or_opt_args("or_opt_best_move", B, n, max_seg)) return rc;
+    if (!tour || !D || !delta || !move || !new_tour)
+        return fail(GNNGLS_ERR_ARG, "or_opt_best_move: NULL pointer (tour, D, delta, move, new_tour)");
+    hipError_t e = gnngls::launch_or_opt_best_move(tour, D, B, n, max_seg, reverse, delta, move, new_tour, (hipStream_t)stream);
+    return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "or_opt_best_move");
+}
+
+int gnngls_or_opt_descent(const int32_t *tour, const double *cost, const double *D, int B, int n, int max_seg, int reverse,
+                          int max_moves, int32_t *tour_out, double *cost_out, int32_t *moves, int32_t *status, double *trace_cost,
+                          int trace_cap, void *stream) {
+    if (int rc = or_opt_args("or_opt_descent", B, n, max_seg)) return rc;
+    if (max_moves < 1) return fail(GNNGLS_ERR_ARG, "or_opt_descent: max_moves=%d must be >= 1 (it bounds the loop)", max_moves);
+    if (trace_cap < 0) return fail(GNNGLS_ERR_ARG, "or_opt_descent: trace_cap=%d must be >= 0", trace_cap);
+    if (!tour || !cost || !D || !tour_out || !cost_out || !moves || !status)
+        return fail(GNNGLS_ERR_ARG, "or_opt_descent: NULL pointer (tour, cost, D, tour_out, cost_out, moves, status)");
+    hipError_t e = gnngls::launch_or_opt_descent(tour, cost, D, B, n, max_seg, reverse, max_moves, tour_out, cost_out, moves, status,
+                                                 trace_cost, trace_cost ? trace_cap : 0, (hipStream_t)stream);
+    return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "or_opt_descent");
 }
 
 static_assert(GNNGLS_SAMPLE_MAX_N == gnngls::kSampleMaxN && GNNGLS_SAMPLE_BAD_WEIGHTS == GNNGLS_SAMPLE_BAD_WEIGHTS_DEV,

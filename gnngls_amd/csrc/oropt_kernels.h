@@ -1,0 +1,34 @@
+// oropt_kernels.h -- internal interface between the Or-opt kernels (oropt_kernels.hip) and the C ABI (capi.hip).
+//
+// Or-opt moves a chain of one to three consecutive tour nodes between two other tour neighbours, forward or reversed; with chains
+// of one node and no reversal it is the reference's relocate (operators.py:76-147).  The candidate (i, L, rev, j), its delta in
+// the reference's operand order, the enumeration order and the descent (local_search, algorithms.py:111-132, with relocate_a2a
+// replaced by the Or-opt scan) are the contract stated in include/gnngls_hip.h.  One workgroup per instance, one launch per batch.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace gnngls {
+
+// a move's selection key holds i and j in ten bits each
+constexpr int kOrOptMaxN = 1024;
+constexpr int kOrOptMaxSeg = 3;
+constexpr int kOrOptStatusAsymmetric = 3;      // GNNGLS_STATUS_ASYMMETRIC
+constexpr int kOrOptStatusMoveCap = 6;         // GNNGLS_STATUS_MOVE_CAP
+
+// tour [B,n+1], D [B,n,n] -> delta [B] (0.0: no move; NaN: the matrix is not bitwise symmetric), move [B,4] = i, L, rev, j (-1s
+// when none), new_tour [B,n+1] (the input when none).  3 <= n <= kOrOptMaxN, 1 <= max_seg <= kOrOptMaxSeg, B >= 1.
+hipError_t launch_or_opt_best_move(const int32_t *tour, const double *D, int B, int n, int max_seg, int reverse, double *delta,
+                                   int32_t *move, int32_t *new_tour, hipStream_t stream);
+
+// the descent: tour [B,n+1], cost [B], D [B,n,n] -> tour_out, cost_out, moves [B], status [B], trace_cost [B,trace_cap] or NULL
+// (the cost after every applied move, the first trace_cap of them).  max_moves >= 1 bounds the loop.
+hipError_t launch_or_opt_descent(const int32_t *tour, const double *cost, const double *D, int B, int n, int max_seg, int reverse,
+                                 int max_moves, int32_t *tour_out, double *cost_out, int32_t *moves, int32_t *status,
+                                 double *trace_cost, int trace_cap, hipStream_t stream);
+
+// workgroup size of the launches for n nodes (one wavefront per 16 nodes, sixteen at most) and their dynamic LDS
+int or_opt_threads(int n);
+int or_opt_lds_bytes(int n);
+
+}  // namespace gnngls

@@ -1,0 +1,267 @@
+// oropt_kernels.hip -- Or-opt on MI355X (gfx950), hand-written HIP: one scan of the segment-move neighbourhood, and the descent
+// that alternates it with 2-opt (the reference's local_search, algorithms.py:111-132, with relocate_a2a replaced).
+//
+// The contract is in include/gnngls_hip.h.  A candidate (i, L, rev, j) takes the chain S = t[i .. i+L-1] out of the tour and puts
+// it back, forward or reversed, at index j of the shortened tour t'.  The kernel names the landing place by the TOUR EDGE it
+// opens instead: edge p = (t[p], t[p+1]) of the unshortened tour, p = j - 1 in front of the chain (p <= i - 2) and p = j - 1 + L
+// behind it (p >= i + L).  Then d = t[p], e = t[p+1] whichever side it is, ascending p is ascending j, and
+//      delta = ((((-D[a,s1] - D[sL,c]) + D[a,c]) - D[d,e]) + D[d,s1]) + D[sL,e]               (rev = 1: ... + D[d,sL]) + D[s1,e])
+// reads tour-edge lengths (a table in LDS: D[a,s1], D[sL,c], D[d,e]), one wave-uniform entry D[a,c], and two entries each of
+// the rows of s1 and sL at the columns t[p], t[p+1] -- the matrix is bitwise symmetric (checked in front of the first scan), so
+// D[d,s1] is read as D[s1][d]: a wavefront gathers from two or three rows of n doubles that stay in the vector L1.
+//
+// Work split: wavefronts over i, lanes over p.  All chains that start at i share the row of s1: a lane loads D[s1][t[p]] and
+// D[s1][t[p+1]] once and evaluates L = 1, 2, 3 and both orientations from at most six gathered entries.  The j-independent prefix
+// (-D[a,s1] - D[sL,c]) + D[a,c] is wave-uniform.  The arg-min is the (delta, key) minimum of gls_common.h with the key
+// (i, L, rev, j) in that order, so the parallel result is the sequential scan's first smallest qualifying candidate.  The 2-opt
+// scan of the descent is the plain one (wavefronts over i, lanes over j); nothing here is pruned.
+//
+// One workgroup per instance, one wavefront per 16 nodes (sixteen at most); the tour (two copies: a move is applied from one into
+// the other) and the edge-length table live in LDS, D stays in global memory (a TSP200 matrix is 320 KB: L2).  The descent's
+// loop applies one move per trip or ends, and ends after max_moves applied moves: no spin-wait, no watchdog, nothing shared
+// between workgroups.  NaNs fail every comparison of the acceptance rule, so such an instance stops at once.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "gls_policy.h"
+#include "oropt_kernels.h"
+
+#pragma clang fp contract(off)
+
+namespace gnngls {
+
+#include "gls_common.h"
+
+namespace {
+
+#ifndef OROPT_NODES_PER_WAVE
+#define OROPT_NODES_PER_WAVE 16        // one wavefront per this many nodes ...
+#endif
+#ifndef OROPT_MAX_WAVES
+#define OROPT_MAX_WAVES 16             // ... and this many wavefronts per instance at most (<= 16: block_reduce_best)
+#endif
+// (measured, scripts/bench_or_opt.py, the descent from the nearest-neighbour start at max_seg 1 / 3: 64 nodes per wavefront and
+// four wavefronts at most took 1.75 / 2.68 ms for 1,024 TSP100 and 3.50 / 5.19 ms for 256 TSP200 instances, 32 and eight 1.04 /
+// 1.64 and 2.26 / 3.49 ms, 16 and sixteen 0.97 / 1.52 and 1.56 / 2.52 ms: a scan is a chain of dependent gathers per row, and
+// more wavefronts keep more rows in flight)
+constexpr int kOrOptWaves = OROPT_MAX_WAVES;
+
+__host__ __device__ inline size_t oropt_r16(size_t x) { return (x + 15) & ~size_t(15); }
+// Ctl | edge lengths [n] fp64 | tour [n+1] | tour [n+1]
+__host__ __device__ inline size_t oropt_lds(int n) {
+    return oropt_r16(sizeof(Ctl)) + oropt_r16((size_t)n * sizeof(double)) + 2 * oropt_r16((size_t)(n + 1) * sizeof(int32_t));
+}
+
+// (i, L, rev, j) in enumeration order: i, j <= 1023
+__device__ __forceinline__ int or_opt_key(int i, int L, int rev, int j) { return (i << 13) | ((L - 1) << 11) | (rev << 10) | j; }
+
+// tour after the move, as a function of the old tour: t'[:j] + S (or S reversed) + t'[j:], t' = t without S
+__device__ __forceinline__ int or_opt_src(int q, int i, int L, int rev, int j) {
+    int r;
+    if (q < j) {
+        r = q;
+    } else if (q < j + L) {
+        const int o = q - j;
+        return i + (rev ? L - 1 - o : o);
+    } else {
+        r = q - L;
+    }
+    return r < i ? r : r + L;
+}
+
+// every thread's best (delta, key) over its share of the 2-opt neighbourhood (operators.py:32-50: 1 <= i < j <= n-1, j - i >= 2;
+// D[a,b] and D[c,d] are tour edges)
+__device__ __forceinline__ void scan_two_opt(const int32_t *t, const double *e, const double *c, int n, int wave, int nwaves, int lane,
+                                             double &bd, int &bk) {
+    for (int i = 1 + wave; i <= n - 3; i += nwaves) {
+        const double *ra = c + (size_t)t[i] * n, *rb = c + (size_t)t[i - 1] * n;
+        const double eab = e[i - 1];
+        for (int j = i + 2 + lane; j <= n - 1; j += kWave) {
+            double delta = ra[t[j]] + rb[t[j - 1]];      // operators.py:25-28, left to right
+            delta = delta - eab;
+            delta = delta - e[j - 1];
+            consider<false>(delta, make_key(i, j), bd, bk);
+        }
+    }
+}
+
+// the same over the Or-opt neighbourhood; lanes own the tour edge p that the chain is put into
+__device__ __forceinline__ void scan_or_opt(const int32_t *t, const double *e, const double *c, int n, int max_seg, int reverse, int wave,
+                                            int nwaves, int lane, double &bd, int &bk) {
+    for (int i = 1 + wave; i <= n - 1; i += nwaves) {
+        const int lmax = max_seg < n - i ? max_seg : n - i;            // i + L - 1 <= n - 1
+        const double *ra = c + (size_t)t[i - 1] * n, *r1 = c + (size_t)t[i] * n, *r2 = r1, *r3 = r1;
+        const double nea = -e[i - 1];
+        const double pre1 = (nea - e[i]) + ra[t[i + 1]];
+        double pre2 = 0.0, pre3 = 0.0;
+        if (lmax >= 2) { r2 = c + (size_t)t[i + 1] * n; pre2 = (nea - e[i + 1]) + ra[t[i + 2]]; }
+        if (lmax >= 3) { r3 = c + (size_t)t[i + 2] * n; pre3 = (nea - e[i + 2]) + ra[t[i + 3]]; }
+        for (int p = lane; p < n; p += kWave) {
+            const bool front = p <= i - 2;               // j = p + 1 <= i - 1; behind the chain j = p + 1 - L >= i + 1
+            if (!front && p <= i) continue;              // an edge of the chain's own ends, whatever L is
+            const bool fwd = !front || p <= i - 3;       // rev == 0 skips j == i - 1 (operators.py:135)
+            const int tp = t[p], tq = t[p + 1];
+            const double ep = e[p];
+            const double x0 = r1[tp], x1 = r1[tq];
+            if (fwd) consider<false>(((pre1 - ep) + x0) + x1, or_opt_key(i, 1, 0, front ? p + 1 : p), bd, bk);
+            if (lmax >= 2 && (front || p >= i + 2)) {
+                const double y0 = r2[tp], y1 = r2[tq];
+                const int j = front ? p + 1 : p - 1;
+                if (fwd) consider<false>(((pre2 - ep) + x0) + y1, or_opt_key(i, 2, 0, j), bd, bk);
+                if (reverse) consider<false>(((pre2 - ep) + y0) + x1, or_opt_key(i, 2, 1, j), bd, bk);
+            }
+            if (lmax >= 3 && (front || p >= i + 3)) {
+                const double z0 = r3[tp], z1 = r3[tq];
+                const int j = front ? p + 1 : p - 2;
+                if (fwd) consider<false>(((pre3 - ep) + x0) + z1, or_opt_key(i, 3, 0, j), bd, bk);
+                if (reverse) consider<false>(((pre3 - ep) + z0) + x1, or_opt_key(i, 3, 1, j), bd, bk);
+            }
+        }
+    }
+}
+
+// the moves are defined for symmetric costs only (rows are read as D[s1][d] for D[d][s1]): one pass over the upper triangle
+// against the lower one, bit by bit
+__device__ __forceinline__ int asymmetric(const double *c, int n, int tid, int nthr) {
+    int bad = 0;
+    for (int i = 0; i < n - 1; ++i)
+        for (int j = i + 1 + tid; j < n; j += nthr)
+            bad |= __double_as_longlong(c[(size_t)i * n + j]) != __double_as_longlong(c[(size_t)j * n + i]);
+    return __syncthreads_or(bad);
+}
+
+__device__ __forceinline__ void edge_lengths(const int32_t *t, const double *c, int n, double *e, int tid, int nthr) {
+    for (int p = tid; p < n; p += nthr) e[p] = c[(size_t)t[p] * n + t[p + 1]];
+}
+
+struct Carve {
+    Ctl *ctl;
+    double *e;
+    int32_t *ta, *tb;
+};
+__device__ __forceinline__ Carve carve(unsigned char *smem, int n) {
+    Carve k;
+    k.ctl = reinterpret_cast<Ctl *>(smem);
+    k.e = reinterpret_cast<double *>(smem + oropt_r16(sizeof(Ctl)));
+    k.ta = reinterpret_cast<int32_t *>(smem + oropt_r16(sizeof(Ctl)) + oropt_r16((size_t)n * sizeof(double)));
+    k.tb = k.ta + oropt_r16((size_t)(n + 1) * sizeof(int32_t)) / sizeof(int32_t);
+    return k;
+}
+
+__global__ __launch_bounds__(kWave *kOrOptWaves) void or_opt_best_move_kernel(const int32_t *tour, const double *D, int n, int max_seg,
+                                                                              int reverse, double *delta, int32_t *move, int32_t *new_tour) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const Carve k = carve(smem, n);
+    const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+    const int lane = tid & (kWave - 1), wave = tid / kWave, nwaves = nthr / kWave;
+    const double *c = D + (size_t)b * n * n;
+    const int32_t *tin = tour + (size_t)b * (n + 1);
+    int32_t *tout = new_tour + (size_t)b * (n + 1);
+
+    for (int q = tid; q <= n; q += nthr) k.ta[q] = tin[q];
+    const int bad = asymmetric(c, n, tid, nthr);         // (its barrier also publishes the tour)
+    double bd = 0.0;
+    int bk = kNoKey;
+    if (!bad) {
+        edge_lengths(k.ta, c, n, k.e, tid, nthr);
+        __syncthreads();
+        int phase = 0;
+        scan_or_opt(k.ta, k.e, c, n, max_seg, reverse, wave, nwaves, lane, bd, bk);
+        block_reduce_best<false>(k.ctl, phase, wave, nwaves, lane, bd, bk);
+    }
+    const bool none = bk == kNoKey;
+    const int i = bk >> 13, L = ((bk >> 11) & 3) + 1, rev = (bk >> 10) & 1, j = bk & 1023;
+    for (int q = tid; q <= n; q += nthr) tout[q] = k.ta[none ? q : or_opt_src(q, i, L, rev, j)];
+    if (tid == 0) {
+        delta[b] = bad ? NAN : bd;
+        int32_t *m = move + (size_t)b * 4;
+        m[0] = none ? -1 : i; m[1] = none ? -1 : L; m[2] = none ? -1 : rev; m[3] = none ? -1 : j;
+    }
+}
+
+__global__ __launch_bounds__(kWave *kOrOptWaves) void or_opt_descent_kernel(const int32_t *tour, const double *cost_in, const double *D, int n,
+                                                                            int max_seg, int reverse, int max_moves, int32_t *tour_out,
+                                                                            double *cost_out, int32_t *moves_out, int32_t *status_out,
+                                                                            double *trace_cost, int trace_cap) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const Carve k = carve(smem, n);
+    const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+    const int lane = tid & (kWave - 1), wave = tid / kWave, nwaves = nthr / kWave;
+    const double *c = D + (size_t)b * n * n;
+    const int32_t *tin = tour + (size_t)b * (n + 1);
+    int32_t *tout = tour_out + (size_t)b * (n + 1);
+
+    int32_t *cur = k.ta, *nxt = k.tb;
+    for (int q = tid; q <= n; q += nthr) cur[q] = tin[q];
+    double cost = cost_in[b];
+    int moves = 0, status = 0;
+    if (asymmetric(c, n, tid, nthr)) {                   // (its barrier also publishes the tour)
+        status = kOrOptStatusAsymmetric;                 // not searched: the outputs are the inputs
+    } else {
+        edge_lengths(cur, c, n, k.e, tid, nthr);
+        __syncthreads();
+        int phase = 0;
+        bool go = true;
+        while (go) {                                     // algorithms.py:116-130; every trip applies a move or is the last
+            bool improved = false;
+            for (int op = 0; op < 2 && go; ++op) {
+                double bd = 0.0;
+                int bk = kNoKey;
+                if (op == 0) scan_two_opt(cur, k.e, c, n, wave, nwaves, lane, bd, bk);
+                else scan_or_opt(cur, k.e, c, n, max_seg, reverse, wave, nwaves, lane, bd, bk);
+                block_reduce_best<false>(k.ctl, phase, wave, nwaves, lane, bd, bk);
+                if (bk == kNoKey) continue;
+                if (op == 0) {
+                    const int i = bk >> 16, j = bk & 0xffff;
+                    for (int q = tid; q <= n; q += nthr) nxt[q] = cur[two_opt_src(q, i, j)];
+                } else {
+                    const int i = bk >> 13, L = ((bk >> 11) & 3) + 1, rev = (bk >> 10) & 1, j = bk & 1023;
+                    for (int q = tid; q <= n; q += nthr) nxt[q] = cur[or_opt_src(q, i, L, rev, j)];
+                }
+                __syncthreads();
+                int32_t *x = cur; cur = nxt; nxt = x;
+                edge_lengths(cur, c, n, k.e, tid, nthr);
+                cost += bd;                              // algorithms.py:124
+                if (tid == 0 && trace_cost && moves < trace_cap) trace_cost[(size_t)b * trace_cap + moves] = cost;
+                ++moves;
+                improved = true;
+                __syncthreads();
+                if (moves >= max_moves) { status = kOrOptStatusMoveCap; go = false; }
+            }
+            if (!improved) go = false;
+        }
+    }
+    for (int q = tid; q <= n; q += nthr) tout[q] = cur[q];
+    if (tid == 0) { cost_out[b] = cost; moves_out[b] = moves; status_out[b] = status; }
+}
+
+}  // namespace
+
+int or_opt_threads(int n) {
+    const int waves = (n + OROPT_NODES_PER_WAVE - 1) / OROPT_NODES_PER_WAVE;
+    return kWave * (waves < kOrOptWaves ? waves : kOrOptWaves);
+}
+
+int or_opt_lds_bytes(int n) { return (int)oropt_lds(n); }
+
+hipError_t launch_or_opt_best_move(const int32_t *tour, const double *D, int B, int n, int max_seg, int reverse, double *delta,
+                                   int32_t *move, int32_t *new_tour, hipStream_t stream) {
+    static_assert(kOrOptMaxN <= 1024 && kOrOptMaxSeg <= 4, "i and j take ten bits of the selection key, L - 1 two");
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(or_opt_best_move_kernel, dim3(B), dim3(or_opt_threads(n)), oropt_lds(n), stream, tour, D, n, max_seg, reverse ? 1 : 0,
+                       delta, move, new_tour);
+    return hipGetLastError();
+}
+
+hipError_t launch_or_opt_descent(const int32_t *tour, const double *cost, const double *D, int B, int n, int max_seg, int reverse,
+                                 int max_moves, int32_t *tour_out, double *cost_out, int32_t *moves, int32_t *status,
+                                 double *trace_cost, int trace_cap, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(or_opt_descent_kernel, dim3(B), dim3(or_opt_threads(n)), oropt_lds(n), stream, tour, cost, D, n, max_seg,
+                       reverse ? 1 : 0, max_moves, tour_out, cost_out, moves, status, trace_cost, trace_cap);
+    return hipGetLastError();
+}
+
+}  // namespace gnngls

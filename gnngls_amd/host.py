@@ -99,6 +99,121 @@ def alpha_nearness(D, pi=None):
     return alpha
 
 
+def _isclose0(delta):
+    """np.isclose(0, delta) with NumPy's defaults, as the reference's acceptance rule evaluates it (operators.py:42,139)."""
+    import numpy as np
+    return np.abs(delta) <= 1e-8 + 1e-5 * np.abs(delta)
+
+
+def or_opt_cost(tour, D, i, L, rev, j):
+    """The delta of the Or-opt candidate (i, L, rev, j) (include/gnngls_hip.h states the definition): the chain S = tour[i..i+L-1]
+    leaves the tour and lands, reversed if rev, at index j of the shortened tour t'.  fp64, left to right as written; for L = 1 it
+    is the reference's relocate_cost (operators.py:83-103) operand by operand."""
+    n = len(tour) - 1
+    assert 1 <= i and i + L - 1 <= n - 1 and 1 <= L and 1 <= j <= n - L and rev in (0, 1)
+    a, s1, sL, c = tour[i - 1], tour[i], tour[i + L - 1], tour[i + L]
+    d = tour[j - 1] if j - 1 < i else tour[j - 1 + L]
+    e = tour[j] if j < i else tour[j + L]
+    if rev:
+        return -D[a, s1] - D[sL, c] + D[a, c] - D[d, e] + D[d, sL] + D[s1, e]
+    return -D[a, s1] - D[sL, c] + D[a, c] - D[d, e] + D[d, s1] + D[sL, e]
+
+
+def or_opt(tour, i, L, rev, j):
+    """The tour after the Or-opt move: t'[:j] + S (or S reversed) + t'[j:] (for L = 1 the reference's relocate,
+    operators.py:76-80)."""
+    tour = list(tour)
+    S = tour[i:i + L]
+    rest = tour[:i] + tour[i + L:]
+    return rest[:j] + (S[::-1] if rev else S) + rest[j:]
+
+
+def two_opt_a2a(tour, D):
+    """The reference's two_opt_a2a, best improvement (operators.py:32-50), vectorised over (i, j) with its operand order:
+    -> (delta, (i, j)) or (0, None)."""
+    import numpy as np
+    t = np.asarray(tour)
+    n = len(t) - 1
+    if n < 4:
+        return 0, None
+    D = np.asarray(D, dtype=np.float64)
+    i = np.arange(1, n - 2)[:, None]
+    j = np.arange(3, n)[None, :]
+    a, b, c, d = t[i], t[i - 1], t[j], t[j - 1]
+    delta = D[a, c] + D[b, d] - D[a, b] - D[c, d]
+    ok = (j - i >= 2) & (delta < 0) & ~_isclose0(delta)
+    if not ok.any():
+        return 0, None
+    m = delta[ok].min()
+    r, col = np.argwhere(ok & (delta == m))[0]            # row-major: the first (i, j) in the reference's order
+    return m, (int(r) + 1, int(col) + 3)
+
+
+def or_opt_a2a(tour, D, max_seg=3, reverse=True):
+    """One best-improvement scan of the Or-opt neighbourhood: every candidate (i, L, rev, j) in ascending lexicographic order,
+    the reference's rule `delta < best_delta and not np.isclose(0, delta)` -- the first candidate with the smallest qualifying
+    delta.  -> (delta, (i, L, rev, j)) or (0, None).  Vectorised over (i, j) per (L, rev) with the operand order of or_opt_cost;
+    with max_seg=1 it is the reference's relocate_a2a (operators.py:129-147)."""
+    import numpy as np
+    assert 1 <= max_seg <= 3
+    t = np.asarray(tour)
+    n = len(t) - 1
+    D = np.asarray(D, dtype=np.float64)
+    best = None                                           # (delta, i, L, rev, j)
+    for L in range(1, min(max_seg, n - 1) + 1):
+        i = np.arange(1, n - L + 1)[:, None]              # i + L - 1 <= n - 1
+        j = np.arange(1, n - L + 1)[None, :]
+        a, s1, sL, c = t[i - 1], t[i], t[i + L - 1], t[i + L]
+        d = t[np.where(j - 1 < i, j - 1, j - 1 + L)]
+        e = t[np.where(j < i, j, j + L)]
+        pre = -D[a, s1] - D[sL, c] + D[a, c] - D[d, e]
+        for rev in ((0, 1) if (reverse and L >= 2) else (0,)):
+            delta = (pre + D[d, sL] + D[s1, e]) if rev else (pre + D[d, s1] + D[sL, e])
+            ok = (j != i) & (delta < 0) & ~_isclose0(delta)
+            if not rev:
+                ok &= j != i - 1                          # operators.py:135
+            if not ok.any():
+                continue
+            m = delta[ok].min()
+            r, col = np.argwhere(ok & (delta == m))[0]    # row-major: the first (i, j) of this (L, rev)
+            cand = (m, int(r) + 1, L, rev, int(col) + 1)
+            if best is None or cand < best:
+                best = cand
+    if best is None:
+        return 0, None
+    return best[0], best[1:]
+
+
+def or_opt_descent(tour, cost, D, max_seg=3, reverse=True, max_moves=None):
+    """The reference's local_search (algorithms.py:111-132), best improvement, with relocate_a2a replaced by or_opt_a2a(max_seg,
+    reverse): two_opt_a2a and or_opt_a2a alternate, cost += delta after each move, until a full pass moves nothing or max_moves
+    moves are applied (checked after every move; None: no cap).  -> (tour, cost, moves, cost_trace): the definition that
+    gnngls_amd.ops.or_opt_descent is compared against bit for bit.  With max_seg=1, reverse=False it is local_search itself."""
+    tour = [int(v) for v in tour]
+    trace = []
+    improved = True
+    while improved:
+        improved = False
+        for op in (0, 1):
+            if op == 0:
+                delta, move = two_opt_a2a(tour, D)
+            else:
+                delta, move = or_opt_a2a(tour, D, max_seg, reverse)
+            if move is None:
+                continue
+            if op == 0:
+                i, j = move
+                tour = tour[:i] + tour[j - 1:i - 1:-1] + tour[j:]      # operators.py:11
+            else:
+                tour = or_opt(tour, *move)
+            cost = cost + delta
+            trace.append(cost)
+            improved = True
+            if max_moves is not None and len(trace) >= max_moves:
+                return tour, cost, len(trace), trace
+    return tour, cost, len(trace), trace
+
+
 def fixed_edge_tour(G, e, scale=None, lkh_path=None, base_tour=None, label_iters=None, perturbation_moves=None, **kwargs):
     """A tour of G that holds edge e (reference __init__.py:63-79: LKH with e fixed).  Here: the fixed-edge search of
     gnngls_amd.labels on the device -- guided_local_search on G's weights with e's weight lowered by M, guide = those weights,

@@ -81,3 +81,32 @@ def relocate_o2a(tour, D, i, first_improvement=False):
 def relocate_a2a(tour, D, first_improvement=False):
     """operators.py:129-147"""
     return _scan(ops.OP_RELOCATE, tour, D, None, first_improvement, relocate)
+
+
+def or_opt(tour, i, L, rev, j):
+    """The Or-opt move (no counterpart in the reference; for L = 1 its relocate, operators.py:76-80): the chain tour[i:i+L] leaves
+    the tour and lands, reversed if rev, at index j of the shortened tour."""
+    rest = tour[:i] + tour[i + L:]
+    S = tour[i:i + L]
+    return rest[:j] + (S[::-1] if rev else S) + rest[j:]
+
+
+def or_opt_cost(tour, D, i, L, rev, j):
+    """The delta of the candidate (i, L, rev, j) as include/gnngls_hip.h defines it (for L = 1 relocate_cost, operators.py:83-103).
+    Four to six matrix entries: evaluated on the host by gnngls_amd.host.or_opt_cost, the definition the kernels are tested
+    against; the scans below run on the GPU."""
+    from . import host
+    if i == j:
+        return 0
+    return float(host.or_opt_cost(tour, np.asarray(D, dtype=np.float64), i, L, int(bool(rev)), j))
+
+
+def or_opt_a2a(tour, D, max_seg=3, reverse=True):
+    """One best-improvement scan of the Or-opt neighbourhood (chains of 1..max_seg nodes, reversed too if `reverse`) in the style
+    of relocate_a2a (operators.py:129-147): -> (delta, new_tour), (0, tour) when nothing qualifies."""
+    t, d = _dev(tour, D)
+    delta, move, _ = ops.or_opt_best_move(t, d, max_seg, reverse)
+    mv = move[0].tolist()
+    if mv[0] < 0:
+        return 0, tour
+    return delta.item(), or_opt(tour, *mv)

@@ -317,6 +317,84 @@ def alpha_nearness(D, pi=None):
     return out
 
 
+OR_OPT_MAX_N = 1024                                           # GNNGLS_OR_OPT_MAX_N
+OR_OPT_MAX_SEG = 3                                            # GNNGLS_OR_OPT_MAX_SEG
+STATUS_MOVE_CAP = 6                                           # GNNGLS_STATUS_MOVE_CAP
+
+
+@dataclass
+class OrOptResult:
+    tour: torch.Tensor           # [B,n+1] int32
+    cost: torch.Tensor           # [B] fp64: the start cost plus the deltas of the applied moves, in order
+    moves: torch.Tensor          # [B] int32 applied moves (2-opt and Or-opt)
+    status: torch.Tensor         # [B] int32 STATUS_OK (a local optimum of both scans) or STATUS_MOVE_CAP
+    trace_cost: torch.Tensor     # [B,trace_cap] fp64 the cost after each of the first trace_cap moves, or None
+
+
+def _or_opt_entry(name):
+    L = _lib.load()
+    if not hasattr(L, name):
+        raise _lib.GnnglsHipError(f"this build of libgnngls_hip.so has no {name}")
+    return getattr(L, name)
+
+
+def _raise_asymmetric(what, bad):
+    raise ValueError(f"{what}: the matrices of instances {bad[:8]} are not bitwise symmetric (status {STATUS_ASYMMETRIC}): "
+                     "the Or-opt kernels read D[d,s] as D[s][d]")
+
+
+def or_opt_best_move(tour, D, max_seg=3, reverse=True):
+    """One best-improvement scan of the Or-opt neighbourhood of every tour of a batch, one launch: a chain of 1..max_seg
+    consecutive nodes moves between two other tour neighbours, forward or (reverse, chains of two and three) reversed
+    (include/gnngls_hip.h states the candidates, the delta and the order; host.or_opt_a2a restates them in NumPy, bit for bit).
+    tour [B,n+1] int32, D [B,n,n] fp64 bitwise symmetric -> (delta [B] fp64, 0.0 when nothing qualifies; move [B,4] int32 =
+    i, L, rev, j, -1s when none; new_tour [B,n+1] int32).  A matrix that is not symmetric raises."""
+    B, n = _check_shapes(tour, D)
+    delta = torch.empty((B,), dtype=torch.float64, device=tour.device)
+    move = torch.empty((B, 4), dtype=torch.int32, device=tour.device)
+    new_tour = torch.empty_like(tour)
+    f = _or_opt_entry("gnngls_or_opt_best_move")
+    _lib.check(f(_lib.ptr(tour.contiguous()), _lib.ptr(D.contiguous()), B, n, int(max_seg), int(bool(reverse)), _lib.ptr(delta),
+                 _lib.ptr(move), _lib.ptr(new_tour), _lib.current_stream()), "or_opt_best_move")
+    bad = torch.isnan(delta).nonzero().flatten().tolist()
+    if bad:
+        _raise_asymmetric("or_opt_best_move", bad)
+    return delta, move, new_tour
+
+
+def or_opt_launch(tour, cost, D, max_seg=3, reverse=True, max_moves=None, trace_cap=0):
+    """The launch behind or_opt_descent and torch.ops.gnngls.or_opt_descent: -> OrOptResult, nothing raised for an instance
+    whose matrix is not symmetric (its status is STATUS_ASYMMETRIC, its outputs are its inputs)."""
+    B, n = _check_shapes(tour, D)
+    assert cost.dtype == torch.float64 and cost.shape == (B,), f"cost shape {tuple(cost.shape)} is not [{B}]"
+    max_moves = 100 * n if max_moves is None else int(max_moves)
+    trace_cap = int(trace_cap)
+    dev = tour.device
+    tour_out = torch.empty_like(tour)
+    cost_out = torch.empty((B,), dtype=torch.float64, device=dev)
+    moves = torch.zeros((B,), dtype=torch.int32, device=dev)
+    status = torch.zeros((B,), dtype=torch.int32, device=dev)
+    trace = torch.zeros((B, trace_cap), dtype=torch.float64, device=dev) if trace_cap > 0 else None
+    f = _or_opt_entry("gnngls_or_opt_descent")
+    _lib.check(f(_lib.ptr(tour.contiguous()), _lib.ptr(cost.contiguous()), _lib.ptr(D.contiguous()), B, n, int(max_seg),
+                 int(bool(reverse)), max_moves, _lib.ptr(tour_out), _lib.ptr(cost_out), _lib.ptr(moves), _lib.ptr(status),
+                 _lib.ptr(trace), trace_cap, _lib.current_stream()), "or_opt_descent")
+    return OrOptResult(tour_out, cost_out, moves, status, trace)
+
+
+def or_opt_descent(tour, cost, D, max_seg=3, reverse=True, max_moves=None, trace_cap=0):
+    """The reference's local_search (algorithms.py:111-132) with relocate_a2a replaced by the Or-opt scan of or_opt_best_move:
+    two_opt_a2a and the Or-opt scan alternate, best improvement, cost += delta after each move, until a full pass moves nothing
+    (status STATUS_OK) or max_moves moves are applied (STATUS_MOVE_CAP; None = 100 * n).  One launch for the batch, bit for bit
+    host.or_opt_descent; with max_seg=1, reverse=False it is local_search itself.  tour [B,n+1] int32, cost [B] fp64, D [B,n,n]
+    fp64 bitwise symmetric -> OrOptResult.  A matrix that is not symmetric raises."""
+    r = or_opt_launch(tour, cost, D, max_seg, reverse, max_moves, trace_cap)
+    bad = (r.status == STATUS_ASYMMETRIC).nonzero().flatten().tolist()
+    if bad:
+        _raise_asymmetric("or_opt_descent", bad)
+    return r
+
+
 def gls_run(D, guides, init_tour, init_cost, perturbation_moves=30, first_improvement=False,
             max_outer_iters=-1, time_limit_s=0.0, watchdog_s=None, trace_cap=0, want_trace_time=False,
             want_penalty=False, penalty_bits=0, retry_overflow=True, imp_cap=0, retry_asymmetric=True):

@@ -82,6 +82,10 @@ class SolveResult:
     # per-instance fields carry: the first with the smallest cost
     start_costs: torch.Tensor = None   # [B,R] fp64
     best_start: torch.Tensor = None    # [B] int64
+    # only with polish="or_opt": best_cost before the polishing descent minus best_cost after it, >= 0 (best_tour / best_cost are
+    # the polished ones)
+    polish_gain: torch.Tensor = None   # [B] fp64
+    polish_time: torch.Tensor = None   # [B] fp64 host time.time() at which the polish of the instance's chunk ended
 
 
 # start tours of solve_batch -> mode of ops.insertion (None: ops.nearest_neighbor)
@@ -108,7 +112,7 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
                 first_improvement=False, max_outer_iters=-1, trace_cap=0, want_trace_time=False, chunk=None,
                 keep_regret=False, budget="per_instance", imp_cap=0, features=None, count_executed=False,
                 init="nearest_neighbor", init_weight="auto", lower_bound=False, bound_iters=2000, starts=1, start_seed=0,
-                alpha_iters=2000):
+                alpha_iters=2000, polish=None, polish_seg=3):
     """D [B,n,n] fp64 CUDA tensor (symmetric).  Returns SolveResult with per-instance tensors.
 
     budget="per_instance" (default, the reference's meaning of --time_limit, test.py:64,92): every instance is searched
@@ -134,12 +138,22 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
     guide is unused).  It needs no model.  The start tour keeps the reference's rule whatever 'alpha' does: alpha is zero on the n
     edges of the minimum 1-tree of every instance and is no matrix to walk greedily.  alpha_iters defaults to bound_iters'
     default, the oracle's 2000: measured (profiles/alpha_guide.json) it gives the best alpha guide wherever the budget is three
-    times the ascent's time or more (0.13 s for 1,024 TSP100, 0.35 s for 256 TSP200 instances); under a shorter budget lower it."""
+    times the ascent's time or more (0.13 s for 1,024 TSP100, 0.35 s for 256 TSP200 instances); under a shorter budget lower it.
+    polish: "or_opt" runs ops.or_opt_descent (2-opt and Or-opt with chains of up to `polish_seg` nodes, reversal on, the default
+    move cap) on the returned best tours after a chunk's search has ended, outside its budget as lower_bound is (with starts > 1
+    on the winner only; with lower_bound before the bound, so that ub is the polished cost).  The polished tours and costs replace
+    best_tour and best_cost; SolveResult.polish_gain [B] = cost before - cost after >= 0, .polish_time, timing["polish_s"].
+    None (default): today's call sequence, polish_gain None, no timing key."""
     if init not in INIT_TOURS:
         raise ValueError(f"unknown start tour {init!r} (one of {', '.join(INIT_TOURS)})")
     if init_weight not in ("auto", "weight"):
         raise ValueError(f"unknown init_weight {init_weight!r} ('auto' or 'weight')")
     insert_mode = INIT_TOURS[init]
+    if polish not in (None, "or_opt"):
+        raise ValueError(f"unknown polish {polish!r} (None or 'or_opt')")
+    polish_seg = int(polish_seg)
+    if polish is not None and not 1 <= polish_seg <= ops.OR_OPT_MAX_SEG:
+        raise ValueError(f"polish_seg={polish_seg} must be in 1..{ops.OR_OPT_MAX_SEG}")
     starts = int(starts)
     if starts < 1:
         raise ValueError(f"starts={starts} must be >= 1")
@@ -166,7 +180,8 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
                            timing={"forward_s": 0.0, "init_s": 0.0, "search_s": 0.0, "chunks": 0},
                            start_time=e64.cpu(), launch_time=e64.cpu(), lower_bound=e64 if lower_bound else None,
                            bound_exit=ei32 if lower_bound else None,
-                           start_costs=e64.reshape(0, starts) if starts > 1 else None, best_start=ei64 if starts > 1 else None)
+                           start_costs=e64.reshape(0, starts) if starts > 1 else None, best_start=ei64 if starts > 1 else None,
+                           polish_gain=e64 if polish else None, polish_time=e64.cpu() if polish else None)
     cap = ops.gls_resident_capacity(n)
     if chunk is None:
         chunk = max((cap if cap > 0 else 64) // starts, 1)
@@ -250,14 +265,24 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
             init_cost = init_cost[win]
             if executed is not None:
                 executed = executed[win]
+        gain = polish_end = None
+        if polish:
+            tp = time.time()
+            po = ops.or_opt_descent(r.best_tour.contiguous(), r.best_cost.contiguous(), Dc, polish_seg, True)
+            gain = r.best_cost - po.cost
+            r = dataclasses.replace(r, best_tour=po.tour, best_cost=po.cost)
+            torch.cuda.synchronize()
+            polish_end = torch.full((Dc.shape[0],), time.time(), dtype=torch.float64)
+            timing["polish_s"] = timing.get("polish_s", 0.0) + (float(polish_end[0]) - tp)
         lb = None
         if lower_bound:
+            tb = time.time() if polish else t3
             lb = ops.one_tree_bound(Dc, r.best_cost, max_iters=bound_iters, want_pi=False)
             torch.cuda.synchronize()
-            timing["bound_s"] = timing.get("bound_s", 0.0) + (time.time() - t3)
+            timing["bound_s"] = timing.get("bound_s", 0.0) + (time.time() - tb)
         outs.append((r, init_cost, R if keep_regret else None,
                      torch.full((Dc.shape[0],), t0, dtype=torch.float64), torch.full((Dc.shape[0],), t2, dtype=torch.float64),
-                     executed, lb, start_costs, best_start))
+                     executed, lb, start_costs, best_start, gain, polish_end))
     cat = lambda xs: torch.cat(xs) if len(xs) > 1 else xs[0]  # noqa: E731
     return SolveResult(
         best_tour=cat([o[0].best_tour for o in outs]), best_cost=cat([o[0].best_cost for o in outs]),
@@ -276,7 +301,9 @@ def solve_batch(D, model=None, scalers=None, guides=("regret_pred",), time_limit
         lower_bound=cat([o[6].bound for o in outs]) if lower_bound else None,
         bound_exit=cat([o[6].exit_kind for o in outs]) if lower_bound else None,
         start_costs=cat([o[7] for o in outs]) if starts > 1 else None,
-        best_start=cat([o[8] for o in outs]) if starts > 1 else None)
+        best_start=cat([o[8] for o in outs]) if starts > 1 else None,
+        polish_gain=cat([o[9] for o in outs]) if polish else None,
+        polish_time=cat([o[10] for o in outs]) if polish else None)
 
 
 def synthetic_model(seed=1234, device="cuda"):

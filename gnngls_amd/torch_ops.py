@@ -1,6 +1,7 @@
 """PyTorch-ROCm custom operators of the hot path: `torch.ops.gnngls.*` (north_star).
 
-Ten operators are registered with `torch.library` over the C ABI of libgnngls_hip.so (include/gnngls_hip.h).  Each has
+Ten operators and, since the Or-opt descent, an eleventh are registered with `torch.library` over the C ABI of libgnngls_hip.so
+(include/gnngls_hip.h).  Each has
 exactly ONE implementation, for the CUDA dispatch key (= HIP on ROCm): there is no CPU kernel behind any of them, so
 calling one with CPU tensors fails in the dispatcher ("no CPU fallback" is structural, not a runtime check).  Shape
 functions (fake/meta kernels) are registered so the ops can be traced and used under FakeTensorMode.  All ops enqueue on
@@ -22,6 +23,9 @@ the current HIP stream, take caller-owned contiguous tensors and retain nothing.
         the Held-Karp 1-tree lower bound of oracle/one_tree.c (in place of Concorde's optimum, scripts/test.py:62,104)
     alpha_nearness(D[B,n,n] f64, pi[B,n] f64 or None) -> alpha[B,n,n] f64
         Helsgaun's alpha-nearness under the potentials of one_tree_bound (None: zeros): a model-free guide for gls_run
+    or_opt_descent(tour, cost[B] f64, D, max_seg, reverse, max_moves, trace_cap) -> (tour, cost, n_moves[B] i32, status[B] i32,
+        trace_cost[B,trace_cap] f64): local_search with Or-opt (chains of 1..max_seg nodes) in relocate's place; status 3 marks an
+        instance whose matrix is not symmetric (outputs = inputs) -- the op reports, gnngls_amd.ops.or_opt_descent raises
     sample_nn_tours(W[B,n,n] f64, R, depot, invert, seed, u[B,R,n-1] f64 or None) -> (tours[B,R,n+1] i32, status[B,R] i32)
         algorithms.py:21-50, R sampled walks per instance; status 6 (and a tour of -1) marks a walk that met weights which are
         no probabilities -- the op reports, gnngls_amd.ops.sample_nn_tours raises
@@ -44,6 +48,7 @@ _LIB.define("insertion(Tensor W, int depot, str mode, Tensor? order) -> Tensor")
 _LIB.define("cheapest_insertion(Tensor sub_tour, Tensor node, Tensor W) -> (Tensor, Tensor)")
 _LIB.define("one_tree_bound(Tensor D, Tensor ub, int max_iters) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("alpha_nearness(Tensor D, Tensor? pi) -> Tensor")
+_LIB.define("or_opt_descent(Tensor tour, Tensor cost, Tensor D, int max_seg, bool reverse, int max_moves, int trace_cap) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("sample_nn_tours(Tensor W, int R, int depot, bool invert, int seed, Tensor? u) -> (Tensor, Tensor)")
 
 _workspaces = {}      # device index -> uint8 scratch tensor for the forward (grown on demand, reused across calls)
@@ -111,6 +116,13 @@ _LIB.impl("insertion", ops.insertion, "CUDA")
 _LIB.impl("cheapest_insertion", ops.cheapest_insertion, "CUDA")
 _LIB.impl("one_tree_bound", _one_tree_bound, "CUDA")
 _LIB.impl("alpha_nearness", ops.alpha_nearness, "CUDA")
+def _or_opt_descent(tour, cost, D, max_seg, reverse, max_moves, trace_cap):
+    r = ops.or_opt_launch(tour, cost, D, max_seg, reverse, max_moves, trace_cap)
+    trace = r.trace_cost if r.trace_cost is not None else torch.zeros((tour.shape[0], 0), dtype=torch.float64, device=tour.device)
+    return r.tour, r.cost, r.moves, r.status, trace
+
+
+_LIB.impl("or_opt_descent", _or_opt_descent, "CUDA")
 _LIB.impl("sample_nn_tours", ops.sample_nn_launch, "CUDA")
 
 
@@ -163,6 +175,14 @@ def _(D, ub, max_iters):
 @torch.library.register_fake("gnngls::alpha_nearness")
 def _(D, pi):
     return D.new_empty(tuple(D.shape), dtype=torch.float64)
+
+
+@torch.library.register_fake("gnngls::or_opt_descent")
+def _(tour, cost, D, max_seg, reverse, max_moves, trace_cap):
+    B = tour.shape[0]
+    i32 = lambda: tour.new_empty((B,), dtype=torch.int32)  # noqa: E731
+    return (tour.new_empty(tuple(tour.shape)), cost.new_empty((B,)), i32(), i32(),
+            cost.new_empty((B, max(int(trace_cap), 0)), dtype=torch.float64))
 
 
 @torch.library.register_fake("gnngls::sample_nn_tours")

@@ -194,6 +194,50 @@ int gnngls_one_tree_bound(const double *D, const double *ub, int B, int n, int m
 #define GNNGLS_ALPHA_MAX_N 1024
 int gnngls_alpha_nearness(const double *D, const double *pi, int B, int n, double *alpha, int32_t *status, void *stream);
 
+/* ---- Or-opt: a chain of one to three consecutive tour nodes moves between two other tour neighbours, forward or reversed ------
+ * The reference's only node-moving operator is relocate (operators.py:76-147), which moves one node; Or-opt is its
+ * generalisation to short chains, the operator KGLS runs beside 2-opt.  Definition (the contract):
+ *   tour t[0..n], t[0] = t[n] = the depot; positions 1..n-1 move, the depot never does.  A candidate is (i, L, rev, j):
+ *   the chain S = t[i .. i+L-1] with 1 <= i, i+L-1 <= n-1, 1 <= L <= max_seg <= GNNGLS_OR_OPT_MAX_SEG; t' = t with S removed
+ *   (length n+1-L; t'[q] = t[q] for q < i, else t[q+L]); j in 1..n-L is the index at which S lands in t' -- the list.insert
+ *   index of the reference's relocate; rev in {0, 1}, rev = 1 only for L >= 2 and only when `reverse` is set.
+ *   a = t[i-1], s1 = t[i], sL = t[i+L-1], c = t[i+L], d = t'[j-1], e = t'[j].
+ *   Skipped: j == i in both orientations (the identity, or an in-place reversal, which 2-opt owns), and rev == 0 with j == i-1
+ *   (the reference's `i - j == 1` rule, operators.py:135).
+ *   delta, fp64, evaluated left to right exactly as written, every operation rounded once:
+ *     rev = 0:  -D[a,s1] - D[sL,c] + D[a,c] - D[d,e] + D[d,s1] + D[sL,e]
+ *     rev = 1:  -D[a,s1] - D[sL,c] + D[a,c] - D[d,e] + D[d,sL] + D[s1,e]
+ *   For L = 1 this is relocate_cost (operators.py:97-102) operand by operand.
+ *   Acceptance is the reference's: delta < best_delta and not np.isclose(0, delta) (operators.py:139).  Candidates are enumerated
+ *   in ascending lexicographic order of (i, L, rev, j); the chosen move is the first candidate with the smallest qualifying
+ *   delta.  The tour after the move is t'[:j] + S (or S reversed) + t'[j:].
+ *   D [B,n,n] must be bitwise symmetric (the kernels read D[d,s1] as D[s1][d]; one pass in front of the first scan checks it);
+ *   tour entries are node ids in 0..n-1 (the kernels clamp nothing).  gnngls_amd.host restates all of it in NumPy.
+ * gnngls_or_opt_best_move: one scan.  delta [B] = the chosen move's delta, 0.0 when no candidate qualifies, NaN for an instance
+ *   whose matrix is not bitwise symmetric; move [B,4] = i, L, rev, j (-1s when none); new_tour [B,n+1] = the tour after the move
+ *   (the input when none).
+ * gnngls_or_opt_descent: local_search (algorithms.py:111-132) with relocate_a2a replaced by the scan above -- two_opt_a2a
+ *   (operators.py:32-50) and the Or-opt scan alternate, best improvement; after each move cost += delta; the loop ends when a
+ *   full pass moves nothing, or after max_moves applied moves (checked after every move).  With max_seg = 1 and reverse = 0 it
+ *   is the reference's local_search bit for bit.
+ *   tour [B,n+1], cost [B] the start tours and their lengths; tour_out, cost_out the result; moves [B] applied moves;
+ *   trace_cost [B,trace_cap] or NULL: the cost after each of the first trace_cap moves (later entries untouched).
+ *   status [B]: GNNGLS_STATUS_OK (a local optimum of both scans), GNNGLS_STATUS_MOVE_CAP (the cap ended the run, even where
+ *   the tour happens to be a local optimum), or GNNGLS_STATUS_ASYMMETRIC (not searched: the outputs are the inputs, 0 moves).
+ *   A NaN fails every comparison of the acceptance rule, so an instance with NaN costs stops at once.
+ * One workgroup per instance, one launch for the batch; the loop is bounded by max_moves: no watchdog, no wall clock.
+ * 3 <= n <= GNNGLS_OR_OPT_MAX_N (a larger n returns GNNGLS_ERR_UNSUPPORTED).  Bad arguments -- a NULL pointer other than
+ * trace_cost, B < 1, n < 3, max_seg outside 1..GNNGLS_OR_OPT_MAX_SEG, max_moves < 1, trace_cap < 0 (GNNGLS_ERR_ARG) -- are
+ * rejected on the host before any device work. */
+#define GNNGLS_OR_OPT_MAX_N 1024
+#define GNNGLS_OR_OPT_MAX_SEG 3
+#define GNNGLS_STATUS_MOVE_CAP 6      /* gnngls_or_opt_descent: max_moves moves were applied and the run ended there */
+int gnngls_or_opt_best_move(const int32_t *tour, const double *D, int B, int n, int max_seg, int reverse, double *delta,
+                            int32_t *move, int32_t *new_tour, void *stream);
+int gnngls_or_opt_descent(const int32_t *tour, const double *cost, const double *D, int B, int n, int max_seg, int reverse,
+                          int max_moves, int32_t *tour_out, double *cost_out, int32_t *moves, int32_t *status, double *trace_cost,
+                          int trace_cap, void *stream);
+
 /* ---- sampled nearest-neighbour walks (algorithms.py:21-50: probabilistic_nearest_neighbour) ----------------------------------
  * R independent walks per instance, one wavefront each, one launch for the B * R walks.  Walk (b, r):
  *   tour = [depot]; at every step i = tour[-1] and the candidates are the unvisited nodes j in ascending id, g_j = W[b,i,j];
