@@ -36,6 +36,7 @@ SIGNATURES = {
     "gnngls_alpha_nearness": [_vp, _vp, _int, _int, _vp, _vp, _vp],
     "gnngls_or_opt_best_move": [_vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp],
     "gnngls_or_opt_descent": [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp],
+    "gnngls_ils_run": [_vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "gnngls_sample_nn_tours": [_vp, _int, _int, _int, _int, _int, _u64, _vp, _vp, _vp, _vp],
     "gnngls_gls_run": [_vp, _vp, _int, _int, _int, _vp, _vp, _int, _int, _int, _i64, _f64, _f64,
                        _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp],
@@ -114,6 +115,8 @@ _SAMPLING = ("gnngls_sample_nn_tours",)
 _ALPHA = ("gnngls_alpha_nearness",)
 # Or-opt (an older build named by GNNGLS_HIP_SO lacks it; ops.or_opt_best_move / or_opt_descent then raise)
 _OR_OPT = ("gnngls_or_opt_best_move", "gnngls_or_opt_descent")
+# iterated local search (an older build named by GNNGLS_HIP_SO lacks it; ops.ils then raises)
+_ILS = ("gnngls_ils_run",)
 _lib = None
 
 
@@ -136,7 +139,7 @@ def load():
         import torch  # noqa: F401
         L = ctypes.CDLL(SO)
         for name, argtypes in SIGNATURES.items():
-            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS or name in _BOUNDS or name in _SAMPLING or name in _ALPHA or name in _OR_OPT) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
+            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS or name in _BOUNDS or name in _SAMPLING or name in _ALPHA or name in _OR_OPT or name in _ILS) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
                 continue              # an older build of the library named by GNNGLS_HIP_SO (same-box A/B of kernel variants)
             f = getattr(L, name)      # AttributeError if the symbol is missing
             f.argtypes = argtypes

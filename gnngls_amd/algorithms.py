@@ -2,7 +2,8 @@
 `insertion`, `local_search`, `guided_local_search` with the reference's signatures, return values and side
 effects, executed by the HIP kernels (the persistent search kernel, the one-launch insertion constructor).
 `alpha_nearness` (no counterpart in the reference) writes a model-free guide attribute for guided_local_search;
-`or_opt_descent` (no counterpart either) is local_search with Or-opt in relocate's place.
+`or_opt_descent` (no counterpart either) is local_search with Or-opt in relocate's place, and `iterated_local_search` is that
+descent inside a loop of double-bridge kicks.
 
 The probabilistic constructors (algorithms.py:21-64: `probabilistic_nearest_neighbour`, `best_probabilistic_nearest_neighbour`)
 have the reference's signatures plus a trailing `seed` and the reference's LAW, not its draws: np.random.choice draws from NumPy's
@@ -164,6 +165,18 @@ def or_opt_descent(init_tour, init_cost, D, max_seg=3, reverse=True):
                            ops.as_dev(np.asarray([init_cost], dtype=np.float64), torch.float64),
                            ops.as_dev(np.asarray(D, dtype=np.float64)[None], torch.float64), max_seg, reverse)
     return r.tour[0].tolist(), r.cost[0].item(), int(r.moves[0])
+
+
+def iterated_local_search(init_tour, init_cost, D, kicks, max_seg=3, reverse=True, seed=None):
+    """Iterated local search on the GPU (ops.ils; no counterpart in the reference): or_opt_descent above, then `kicks` times a
+    double-bridge kick of the accepted tour, the same descent, and the better tour kept -> (tour, cost, costs_per_kick), the last
+    the cost the descent reached after each kick.  seed=None takes the seed as ONE draw from NumPy's global stream."""
+    seed = _draw_seed(seed)
+    r = ops.ils(ops.as_dev(np.asarray(init_tour, dtype=np.int32)[None], torch.int32),
+                ops.as_dev(np.asarray([init_cost], dtype=np.float64), torch.float64),
+                ops.as_dev(np.asarray(D, dtype=np.float64)[None], torch.float64), int(kicks), max_seg, reverse, seed=seed,
+                want_trace=True)
+    return r.tour[0].tolist(), r.cost[0].item(), r.trace_cost[0].tolist()
 
 
 def guided_local_search(G, init_tour, init_cost, t_lim, weight="weight", guides=["weight"], perturbation_moves=30,

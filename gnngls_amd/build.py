@@ -34,8 +34,8 @@ HEADERS = {
     "constructors_kernels.hip": ["constructors_kernels.h", "gls_common.h", "gls_policy.h"],
     "bounds_kernels.hip": ["bounds_kernels.h", "gls_common.h", "gls_policy.h"],
     "alpha_kernels.hip": ["alpha_kernels.h", "gls_common.h", "gls_policy.h"],
-    "oropt_kernels.hip": ["oropt_kernels.h", "gls_common.h", "gls_policy.h"],
-    "sampling_kernels.hip": ["sampling_kernels.h"],
+    "oropt_kernels.hip": ["oropt_kernels.h", "gls_common.h", "gls_policy.h", "philox.h"],
+    "sampling_kernels.hip": ["sampling_kernels.h", "philox.h"],
     "capi.hip": ["gls_kernels.h", "gls_plan.h", "gls_policy.h", "model_kernels.h", "model_plan.h", "model_policy.h", "train_kernels.h", "heads_kernels.h",
                  "labels_kernels.h", "constructors_kernels.h", "bounds_kernels.h", "alpha_kernels.h", "oropt_kernels.h", "sampling_kernels.h", os.path.join("..", "..", "include", "gnngls_hip.h")],
 }

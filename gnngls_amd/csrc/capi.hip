@@ -321,6 +321,23 @@ int gnngls_or_opt_descent(const int32_t *tour, const double *cost, const double 
     return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "or_opt_descent");
 }
 
+int gnngls_ils_run(const int32_t *tour, const double *cost, const double *D, int B, int n, int kicks, int kick0, int max_seg, int reverse,
+                   int max_moves, uint64_t seed, const double *u, int32_t *tour_out, double *cost_out, int32_t *moves, int32_t *accepted,
+                   int32_t *status, double *trace_cost, void *stream) {
+    if (n < 4) return fail(GNNGLS_ERR_ARG, "ils_run: n=%d must be >= 4 (a double bridge cuts the tour into four pieces)", n);
+    if (int rc = or_opt_args("ils_run", B, n, max_seg)) return rc;
+    if (kicks < 0) return fail(GNNGLS_ERR_ARG, "ils_run: kicks=%d must be >= 0", kicks);
+    if (kick0 < 0) return fail(GNNGLS_ERR_ARG, "ils_run: kick0=%d must be >= 0", kick0);
+    if ((long long)kick0 + kicks > 0x7fffffffLL)
+        return fail(GNNGLS_ERR_ARG, "ils_run: kick0 + kicks = %lld exceeds 2^31 - 1 (the kick counter)", (long long)kick0 + kicks);
+    if (max_moves < 1) return fail(GNNGLS_ERR_ARG, "ils_run: max_moves=%d must be >= 1 (with kicks it bounds the loop)", max_moves);
+    if (!tour || !cost || !D || !tour_out || !cost_out || !moves || !accepted || !status)
+        return fail(GNNGLS_ERR_ARG, "ils_run: NULL pointer (tour, cost, D, tour_out, cost_out, moves, accepted, status)");
+    hipError_t e = gnngls::launch_ils(tour, cost, D, B, n, kicks, kick0, max_seg, reverse, max_moves, seed, u, tour_out, cost_out, moves,
+                                      accepted, status, trace_cost, (hipStream_t)stream);
+    return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "ils_run");
+}
+
 static_assert(GNNGLS_SAMPLE_MAX_N == gnngls::kSampleMaxN && GNNGLS_SAMPLE_BAD_WEIGHTS == GNNGLS_SAMPLE_BAD_WEIGHTS_DEV,
               "include/gnngls_hip.h and sampling_kernels.h disagree");
 

@@ -27,6 +27,14 @@ hipError_t launch_or_opt_descent(const int32_t *tour, const double *cost, const 
                                  int max_moves, int32_t *tour_out, double *cost_out, int32_t *moves, int32_t *status,
                                  double *trace_cost, int trace_cap, hipStream_t stream);
 
+// iterated local search (the contract is in include/gnngls_hip.h): the descent above, then `kicks` times a double-bridge kick of
+// the accepted tour, a descent of the kicked tour, and the better of the two kept.  u [B,kicks,3] uniforms or NULL (Philox,
+// counter (b, kick0 + k, s, 1)); trace_cost [B,kicks] or NULL: the candidate's cost after every kick.  4 <= n <= kOrOptMaxN,
+// kicks >= 0, kick0 >= 0, max_moves >= 1 bounds the applied moves of the whole run.
+hipError_t launch_ils(const int32_t *tour, const double *cost, const double *D, int B, int n, int kicks, int kick0, int max_seg, int reverse,
+                      int max_moves, uint64_t seed, const double *u, int32_t *tour_out, double *cost_out, int32_t *moves,
+                      int32_t *accepted, int32_t *status, double *trace_cost, hipStream_t stream);
+
 // workgroup size of the launches for n nodes (one wavefront per 16 nodes, sixteen at most) and their dynamic LDS
 int or_opt_threads(int n);
 int or_opt_lds_bytes(int n);

@@ -20,6 +20,12 @@
 // the other) and the edge-length table live in LDS, D stays in global memory (a TSP200 matrix is 320 KB: L2).  The descent's
 // loop applies one move per trip or ends, and ends after max_moves applied moves: no spin-wait, no watchdog, nothing shared
 // between workgroups.  NaNs fail every comparison of the acceptance rule, so such an instance stops at once.
+//
+// Iterated local search (ils_kernel) is that descent inside a loop of double-bridge kicks, all of it in one launch: the accepted
+// tour keeps a third LDS buffer of its own while the kicked candidate descends in the ping-pong pair, so accepting a candidate
+// is a swap of three pointers and rejecting one costs nothing.  The cut points of a kick come from the caller's uniforms or
+// from philox.h; cut points, kick delta, acceptance, the move cap and the symmetry verdict are computed by every thread from
+// the same values (kernel arguments, read-only global memory, LDS behind a barrier), so every branch around a barrier is uniform.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -27,6 +33,7 @@
 
 #include "gls_policy.h"
 #include "oropt_kernels.h"
+#include "philox.h"
 
 #pragma clang fp contract(off)
 
@@ -53,6 +60,9 @@ __host__ __device__ inline size_t oropt_r16(size_t x) { return (x + 15) & ~size_
 __host__ __device__ inline size_t oropt_lds(int n) {
     return oropt_r16(sizeof(Ctl)) + oropt_r16((size_t)n * sizeof(double)) + 2 * oropt_r16((size_t)(n + 1) * sizeof(int32_t));
 }
+
+// the same and a third tour buffer: iterated local search keeps the accepted tour beside the ping-pong pair
+__host__ __device__ inline size_t ils_lds(int n) { return oropt_lds(n) + oropt_r16((size_t)(n + 1) * sizeof(int32_t)); }
 
 // (i, L, rev, j) in enumeration order: i, j <= 1023
 __device__ __forceinline__ int or_opt_key(int i, int L, int rev, int j) { return (i << 13) | ((L - 1) << 11) | (rev << 10) | j; }
@@ -139,7 +149,7 @@ __device__ __forceinline__ void edge_lengths(const int32_t *t, const double *c, 
 struct Carve {
     Ctl *ctl;
     double *e;
-    int32_t *ta, *tb;
+    int32_t *ta, *tb, *tc;                               // tc: ils_kernel only (ils_lds)
 };
 __device__ __forceinline__ Carve carve(unsigned char *smem, int n) {
     Carve k;
@@ -147,7 +157,46 @@ __device__ __forceinline__ Carve carve(unsigned char *smem, int n) {
     k.e = reinterpret_cast<double *>(smem + oropt_r16(sizeof(Ctl)));
     k.ta = reinterpret_cast<int32_t *>(smem + oropt_r16(sizeof(Ctl)) + oropt_r16((size_t)n * sizeof(double)));
     k.tb = k.ta + oropt_r16((size_t)(n + 1) * sizeof(int32_t)) / sizeof(int32_t);
+    k.tc = k.tb + oropt_r16((size_t)(n + 1) * sizeof(int32_t)) / sizeof(int32_t);
     return k;
+}
+
+// the descent (algorithms.py:111-132 with relocate_a2a replaced by the Or-opt scan) from the tour in cur, whose edge lengths are
+// in e behind a barrier; it leaves the same state.  cur / nxt swap with every move; cost, moves and status carry on from what
+// the caller holds (moves counts against max_moves across calls), trace: the cost after move m at trace[m], m < trace_cap.
+// Every thread takes the same trips: bd / bk come out of block_reduce_best uniform, the rest is arguments.
+__device__ __forceinline__ void descend(int32_t *&cur, int32_t *&nxt, double *e, Ctl *ctl, int &phase, const double *c, int n, int max_seg,
+                                        int reverse, int max_moves, int tid, int nthr, int lane, int wave, int nwaves, double &cost,
+                                        int &moves, int &status, double *trace, int trace_cap) {
+    bool go = true;
+    while (go) {                                         // algorithms.py:116-130; every trip applies a move or is the last
+        bool improved = false;
+        for (int op = 0; op < 2 && go; ++op) {
+            double bd = 0.0;
+            int bk = kNoKey;
+            if (op == 0) scan_two_opt(cur, e, c, n, wave, nwaves, lane, bd, bk);
+            else scan_or_opt(cur, e, c, n, max_seg, reverse, wave, nwaves, lane, bd, bk);
+            block_reduce_best<false>(ctl, phase, wave, nwaves, lane, bd, bk);
+            if (bk == kNoKey) continue;
+            if (op == 0) {
+                const int i = bk >> 16, j = bk & 0xffff;
+                for (int q = tid; q <= n; q += nthr) nxt[q] = cur[two_opt_src(q, i, j)];
+            } else {
+                const int i = bk >> 13, L = ((bk >> 11) & 3) + 1, rev = (bk >> 10) & 1, j = bk & 1023;
+                for (int q = tid; q <= n; q += nthr) nxt[q] = cur[or_opt_src(q, i, L, rev, j)];
+            }
+            __syncthreads();
+            int32_t *x = cur; cur = nxt; nxt = x;
+            edge_lengths(cur, c, n, e, tid, nthr);
+            cost += bd;                                  // algorithms.py:124
+            if (tid == 0 && trace && moves < trace_cap) trace[moves] = cost;
+            ++moves;
+            improved = true;
+            __syncthreads();
+            if (moves >= max_moves) { status = kOrOptStatusMoveCap; go = false; }
+        }
+        if (!improved) go = false;
+    }
 }
 
 __global__ __launch_bounds__(kWave *kOrOptWaves) void or_opt_best_move_kernel(const int32_t *tour, const double *D, int n, int max_seg,
@@ -203,38 +252,99 @@ __global__ __launch_bounds__(kWave *kOrOptWaves) void or_opt_descent_kernel(cons
         edge_lengths(cur, c, n, k.e, tid, nthr);
         __syncthreads();
         int phase = 0;
-        bool go = true;
-        while (go) {                                     // algorithms.py:116-130; every trip applies a move or is the last
-            bool improved = false;
-            for (int op = 0; op < 2 && go; ++op) {
-                double bd = 0.0;
-                int bk = kNoKey;
-                if (op == 0) scan_two_opt(cur, k.e, c, n, wave, nwaves, lane, bd, bk);
-                else scan_or_opt(cur, k.e, c, n, max_seg, reverse, wave, nwaves, lane, bd, bk);
-                block_reduce_best<false>(k.ctl, phase, wave, nwaves, lane, bd, bk);
-                if (bk == kNoKey) continue;
-                if (op == 0) {
-                    const int i = bk >> 16, j = bk & 0xffff;
-                    for (int q = tid; q <= n; q += nthr) nxt[q] = cur[two_opt_src(q, i, j)];
-                } else {
-                    const int i = bk >> 13, L = ((bk >> 11) & 3) + 1, rev = (bk >> 10) & 1, j = bk & 1023;
-                    for (int q = tid; q <= n; q += nthr) nxt[q] = cur[or_opt_src(q, i, L, rev, j)];
-                }
-                __syncthreads();
-                int32_t *x = cur; cur = nxt; nxt = x;
-                edge_lengths(cur, c, n, k.e, tid, nthr);
-                cost += bd;                              // algorithms.py:124
-                if (tid == 0 && trace_cost && moves < trace_cap) trace_cost[(size_t)b * trace_cap + moves] = cost;
-                ++moves;
-                improved = true;
-                __syncthreads();
-                if (moves >= max_moves) { status = kOrOptStatusMoveCap; go = false; }
-            }
-            if (!improved) go = false;
-        }
+        descend(cur, nxt, k.e, k.ctl, phase, c, n, max_seg, reverse, max_moves, tid, nthr, lane, wave, nwaves, cost, moves, status,
+                trace_cost ? trace_cost + (size_t)b * trace_cap : nullptr, trace_cap);
     }
     for (int q = tid; q <= n; q += nthr) tout[q] = cur[q];
     if (tid == 0) { cost_out[b] = cost; moves_out[b] = moves; status_out[b] = status; }
+}
+
+// min(int(u * k), k - 1), clamped below at 0, k >= 1: one fp64 multiply, truncated.  Every conversion is of a value in
+// [0, k); a u outside [0, 1) or a NaN lands on an end of the range
+__device__ __forceinline__ int cut_offset(double u, int k) {
+    const double x = u * (double)k;
+    if (!(x >= 0.0)) return 0;
+    return x < (double)k ? (int)x : k - 1;
+}
+
+// tour after the orientation-preserving double bridge A D C B, as a function of the old tour: A = t[0:p1], B = t[p1:p2],
+// C = t[p2:p3], D = t[p3:n]; position n (the depot) stays
+__device__ __forceinline__ int double_bridge_src(int q, int p1, int p2, int p3, int n) {
+    if (q < p1 || q >= n) return q;
+    const int d_end = p1 + (n - p3), c_end = d_end + (p3 - p2);
+    if (q < d_end) return p3 + (q - p1);
+    if (q < c_end) return p2 + (q - d_end);
+    return p1 + (q - c_end);
+}
+
+// iterated local search: descent, then `kicks` times { double bridge on the accepted tour, descent, keep the better tour }
+__global__ __launch_bounds__(kWave *kOrOptWaves) void ils_kernel(const int32_t *tour, const double *cost_in, const double *D, int n, int kicks,
+                                                                 int kick0, int max_seg, int reverse, int max_moves, uint64_t seed,
+                                                                 const double *u, int32_t *tour_out, double *cost_out, int32_t *moves_out,
+                                                                 int32_t *accepted_out, int32_t *status_out, double *trace_cost) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const Carve k = carve(smem, n);
+    const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+    const int lane = tid & (kWave - 1), wave = tid / kWave, nwaves = nthr / kWave;
+    const double *c = D + (size_t)b * n * n;
+    const int32_t *tin = tour + (size_t)b * (n + 1);
+    int32_t *tout = tour_out + (size_t)b * (n + 1);
+    const double *ub = u ? u + (size_t)b * kicks * 3 : nullptr;
+
+    int32_t *acc = k.ta, *ping = k.tb, *pong = k.tc;      // the accepted tour, and the pair a candidate descends in
+    for (int q = tid; q <= n; q += nthr) acc[q] = tin[q];
+    double acc_cost = cost_in[b];
+    int moves = 0, status = 0, accepted = 0;
+    if (asymmetric(c, n, tid, nthr)) {                   // (its barrier also publishes the tour)
+        status = kOrOptStatusAsymmetric;                 // not searched: the outputs are the inputs
+    } else {
+        edge_lengths(acc, c, n, k.e, tid, nthr);
+        __syncthreads();
+        int phase = 0;
+        descend(acc, ping, k.e, k.ctl, phase, c, n, max_seg, reverse, max_moves, tid, nthr, lane, wave, nwaves, acc_cost, moves, status,
+                nullptr, 0);
+        const int m = n - 1;
+        for (int kick = 0; kick < kicks && status == 0; ++kick) {     // status: uniform (descend), so is every trip
+            double u0, u1, u2;
+            if (ub) {
+                u0 = ub[(size_t)kick * 3]; u1 = ub[(size_t)kick * 3 + 1]; u2 = ub[(size_t)kick * 3 + 2];
+            } else {
+                const uint32_t kc = (uint32_t)kick0 + (uint32_t)kick;
+                u0 = philox_uniform53(seed, (uint32_t)b, kc, 0u, 1u);
+                u1 = philox_uniform53(seed, (uint32_t)b, kc, 1u, 1u);
+                u2 = philox_uniform53(seed, (uint32_t)b, kc, 2u, 1u);
+            }
+            const int p1 = 1 + cut_offset(u0, m - 2);                  // 1 .. m-2
+            const int p2 = p1 + 1 + cut_offset(u1, m - 1 - p1);        // p1+1 .. m-1
+            const int p3 = p2 + 1 + cut_offset(u2, m - p2);            // p2+1 .. m
+            __syncthreads();                             // the last scans of the descent before have read ping / pong
+            const int ae = acc[p1 - 1], bs = acc[p1], be = acc[p2 - 1], cs = acc[p2], ce = acc[p3 - 1], ds = acc[p3], de = acc[n - 1],
+                      z = acc[n];
+            double delta = c[(size_t)ae * n + ds] + c[(size_t)de * n + cs];
+            delta = delta + c[(size_t)ce * n + bs];
+            delta = delta + c[(size_t)be * n + z];
+            delta = delta - c[(size_t)ae * n + bs];
+            delta = delta - c[(size_t)be * n + cs];
+            delta = delta - c[(size_t)ce * n + ds];
+            delta = delta - c[(size_t)de * n + z];
+            for (int q = tid; q <= n; q += nthr) ping[q] = acc[double_bridge_src(q, p1, p2, p3, n)];
+            __syncthreads();
+            edge_lengths(ping, c, n, k.e, tid, nthr);
+            __syncthreads();
+            double cand_cost = acc_cost + delta;
+            descend(ping, pong, k.e, k.ctl, phase, c, n, max_seg, reverse, max_moves, tid, nthr, lane, wave, nwaves, cand_cost, moves,
+                    status, nullptr, 0);                 // the candidate ends in ping, pong is the free one
+            if (tid == 0 && trace_cost) trace_cost[((size_t)b * kicks + kick)] = cand_cost;
+            const double d = cand_cost - acc_cost;
+            if (d < 0.0 && !close_to_zero(d)) {          // operators.py:42 on the kick; uniform
+                int32_t *x = acc; acc = ping; ping = x;
+                acc_cost = cand_cost;
+                ++accepted;
+            }
+        }
+    }
+    for (int q = tid; q <= n; q += nthr) tout[q] = acc[q];
+    if (tid == 0) { cost_out[b] = acc_cost; moves_out[b] = moves; accepted_out[b] = accepted; status_out[b] = status; }
 }
 
 }  // namespace
@@ -261,6 +371,15 @@ hipError_t launch_or_opt_descent(const int32_t *tour, const double *cost, const 
     (void)hipGetLastError();
     hipLaunchKernelGGL(or_opt_descent_kernel, dim3(B), dim3(or_opt_threads(n)), oropt_lds(n), stream, tour, cost, D, n, max_seg,
                        reverse ? 1 : 0, max_moves, tour_out, cost_out, moves, status, trace_cost, trace_cap);
+    return hipGetLastError();
+}
+
+hipError_t launch_ils(const int32_t *tour, const double *cost, const double *D, int B, int n, int kicks, int kick0, int max_seg, int reverse,
+                      int max_moves, uint64_t seed, const double *u, int32_t *tour_out, double *cost_out, int32_t *moves,
+                      int32_t *accepted, int32_t *status, double *trace_cost, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(ils_kernel, dim3(B), dim3(or_opt_threads(n)), ils_lds(n), stream, tour, cost, D, n, kicks, kick0, max_seg,
+                       reverse ? 1 : 0, max_moves, seed, u, tour_out, cost_out, moves, accepted, status, trace_cost);
     return hipGetLastError();
 }
 

@@ -19,6 +19,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "philox.h"
 #include "sampling_kernels.h"
 
 #pragma clang fp contract(off)
@@ -29,24 +30,9 @@ namespace {
 
 constexpr int kLanes = 64;
 
-// Philox4x32-10 (Salmon et al., SC'11): counter (c0, c1, c2, c3), key (k0, k1) -> the first two output words
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t &o0, uint32_t &o1) {
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    o0 = c0; o1 = c1;
-}
-
+// the walks' stream of philox.h: counter (b, r, step, 0)
 __device__ __forceinline__ double uniform53(uint64_t seed, uint32_t b, uint32_t r, uint32_t s) {
-    uint32_t o0, o1;
-    philox4x32_10(b, r, s, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), o0, o1);
-    return (double)((((uint64_t)o0 << 32) | o1) >> 11) * 0x1.0p-53;
+    return philox_uniform53(seed, b, r, s, 0u);
 }
 
 // inclusive doubling scan over the 64 lanes: round d adds the value lane l - d held before the round

@@ -214,6 +214,106 @@ def or_opt_descent(tour, cost, D, max_seg=3, reverse=True, max_moves=None):
     return tour, cost, len(trace), trace
 
 
+def double_bridge_cuts(u, n):
+    """The cut points (p1, p2, p3) of a double-bridge kick from three uniforms in [0,1), 1 <= p1 < p2 < p3 <= n-1, n >= 4
+    (include/gnngls_hip.h states the definition): with m = n - 1 each product is one fp64 multiply, truncated toward zero, then
+    clamped into its range."""
+    u0, u1, u2 = (float(x) for x in u)
+    m = n - 1
+    assert m >= 3
+    p1 = 1 + min(int(u0 * (m - 2)), m - 3)
+    p2 = p1 + 1 + min(int(u1 * (m - 1 - p1)), m - 2 - p1)
+    p3 = p2 + 1 + min(int(u2 * (m - p2)), m - 1 - p2)
+    return p1, p2, p3
+
+
+def double_bridge(tour, p1, p2, p3):
+    """The tour after the orientation-preserving double bridge: with A = t[0:p1], B = t[p1:p2], C = t[p2:p3], Dseg = t[p3:n] it
+    is A + Dseg + C + B + [t[n]] -- A D C B: all four junctions are new, the depot never moves."""
+    tour = list(tour)
+    n = len(tour) - 1
+    assert 1 <= p1 < p2 < p3 <= n - 1
+    return tour[:p1] + tour[p3:n] + tour[p2:p3] + tour[p1:p2] + [tour[n]]
+
+
+def double_bridge_cost(tour, D, p1, p2, p3):
+    """The delta of that kick: the four new junctions minus the four old ones, fp64, left to right as written."""
+    n = len(tour) - 1
+    assert 1 <= p1 < p2 < p3 <= n - 1
+    ae, bs, be, cs, ce, ds, de, z = tour[p1 - 1], tour[p1], tour[p2 - 1], tour[p2], tour[p3 - 1], tour[p3], tour[n - 1], tour[n]
+    return D[ae, ds] + D[de, cs] + D[ce, bs] + D[be, z] - D[ae, bs] - D[be, cs] - D[ce, ds] - D[de, z]
+
+
+def philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (Salmon et al., SC'11) on uint64 arrays that hold 32-bit words: counter (c0, c1, c2, c3), key (k0, k1) ->
+    the four output words.  The device generator (csrc/philox.h) in NumPy."""
+    import numpy as np
+    m32, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) for c in (c0, c1, c2, c3))
+    k0, k1 = np.uint64(k0), np.uint64(k1)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2       # 32 x 32 bits: no overflow of 64
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & m32, (p0 >> s32) ^ c3 ^ k1, p0 & m32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+    return c0, c1, c2, c3
+
+
+def philox_uniforms(seed, B, K, S, b0=0, k0=0, c3=0):
+    """The device's uniforms u[b,k,s] for b = b0 .. b0+B-1, k = k0 .. k0+K-1, s = 0 .. S-1: [B,K,S] fp64 in [0,1).  Key
+    (seed & 0xffffffff, seed >> 32), counter (b, k, s, c3), u = ((o0 << 32 | o1) >> 11) * 2^-53.  c3 = 0 is the stream of the
+    sampled walks (b, r, step, 0), c3 = 1 the stream of the double-bridge kicks (b, kick0 + k, s, 1)."""
+    import numpy as np
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    b, k, s = np.meshgrid(np.arange(b0, b0 + B, dtype=np.uint64), np.arange(k0, k0 + K, dtype=np.uint64),
+                          np.arange(S, dtype=np.uint64), indexing="ij")
+    o0, o1, _, _ = philox4x32_10(b, k, s, np.full_like(b, c3), seed & 0xFFFFFFFF, seed >> 32)
+    return (((o0 << np.uint64(32)) | o1) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+
+
+ILS_STATUS_MOVE_CAP = 6                                   # GNNGLS_STATUS_MOVE_CAP
+
+
+def ils(tour, cost, D, kicks, max_seg=3, reverse=True, max_moves=None, u=None, seed=0, b=0, kick0=0):
+    """Iterated local search of one instance in NumPy, the definition of include/gnngls_hip.h restated -- what gnngls_amd.ops.ils
+    is compared against bit for bit.
+      1. cur, cur_cost = or_opt_descent(tour, cost).
+      2. for k = 0 .. kicks-1: (p1, p2, p3) = double_bridge_cuts(u[k]); cand = double_bridge(cur), cand_cost = cur_cost +
+         double_bridge_cost; cand, cand_cost = or_opt_descent(cand, cand_cost); trace[k] = cand_cost; d = cand_cost - cur_cost;
+         accept iff d < 0 and not np.isclose(0, d) (operators.py:42 applied to the kick): cur, cur_cost = cand, cand_cost.
+      3. max_moves (None: no cap) caps the applied descent moves of the whole run, checked after every move: the descent in
+         progress ends there, step 2's bookkeeping is applied to what it holds, the run ends with status ILS_STATUS_MOVE_CAP.
+    u [kicks,3] uniforms in [0,1), or None: philox_uniforms(seed, 1, kicks, 3, b0=b, k0=kick0, c3=1)[0], the draws the device
+    makes for instance b of a batch.  With kick0 a run continues an earlier one: K1 kicks, then K2 kicks with kick0 = K1 from
+    the first run's outputs, is the run of K1 + K2 kicks.  -> (tour, cost, moves, accepted, status, trace)."""
+    import numpy as np
+    n = len(tour) - 1
+    assert n >= 4 and kicks >= 0 and kick0 >= 0
+    if u is None:
+        u = philox_uniforms(seed, 1, kicks, 3, b0=b, k0=kick0, c3=1)[0]
+    u = np.asarray(u, dtype=np.float64).reshape(kicks, 3)
+
+    def left(moves):
+        return None if max_moves is None else max_moves - moves
+
+    cur, cur_cost, moves, _ = or_opt_descent(tour, cost, D, max_seg, reverse, left(0))
+    accepted, trace = 0, []
+    capped = max_moves is not None and moves >= max_moves
+    for k in range(kicks):
+        if capped:
+            break
+        p1, p2, p3 = double_bridge_cuts(u[k], n)
+        cand_cost = cur_cost + double_bridge_cost(cur, D, p1, p2, p3)
+        cand, cand_cost, m, _ = or_opt_descent(double_bridge(cur, p1, p2, p3), cand_cost, D, max_seg, reverse, left(moves))
+        moves += m
+        capped = max_moves is not None and moves >= max_moves
+        trace.append(cand_cost)
+        d = cand_cost - cur_cost
+        if d < 0 and not _isclose0(d):
+            cur, cur_cost = cand, cand_cost
+            accepted += 1
+    return cur, cur_cost, moves, accepted, ILS_STATUS_MOVE_CAP if capped else 0, trace
+
+
 def fixed_edge_tour(G, e, scale=None, lkh_path=None, base_tour=None, label_iters=None, perturbation_moves=None, **kwargs):
     """A tour of G that holds edge e (reference __init__.py:63-79: LKH with e fixed).  Here: the fixed-edge search of
     gnngls_amd.labels on the device -- guided_local_search on G's weights with e's weight lowered by M, guide = those weights,

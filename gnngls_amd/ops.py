@@ -395,6 +395,57 @@ def or_opt_descent(tour, cost, D, max_seg=3, reverse=True, max_moves=None, trace
     return r
 
 
+@dataclass
+class IlsResult:
+    tour: torch.Tensor           # [B,n+1] int32 the accepted tour
+    cost: torch.Tensor           # [B] fp64 its accumulated cost
+    moves: torch.Tensor          # [B] int32 applied descent moves of the whole run, the first descent's included
+    accepted: torch.Tensor       # [B] int32 accepted kicks
+    status: torch.Tensor         # [B] int32 STATUS_OK, STATUS_MOVE_CAP or (ils_launch only) STATUS_ASYMMETRIC
+    trace_cost: torch.Tensor     # [B,kicks] fp64 the candidate's cost after every kick (NaN: the kick never ran), or None
+
+
+def ils_launch(tour, cost, D, kicks, max_seg=3, reverse=True, max_moves=None, seed=0, u=None, kick0=0, want_trace=False):
+    """The launch behind ils and torch.ops.gnngls.ils: -> IlsResult, nothing raised for an instance whose matrix is not symmetric
+    (its status is STATUS_ASYMMETRIC, its outputs are its inputs)."""
+    B, n = _check_shapes(tour, D)
+    assert cost.dtype == torch.float64 and cost.shape == (B,), f"cost shape {tuple(cost.shape)} is not [{B}]"
+    kicks, kick0 = int(kicks), int(kick0)
+    if u is not None:
+        assert u.dtype == torch.float64 and u.shape == (B, kicks, 3), f"u shape {tuple(u.shape)} is not [{B},{kicks},3]"
+        u = u.to(tour.device).contiguous()
+    max_moves = min(100 * n * (kicks + 1), 2 ** 31 - 1) if max_moves is None else int(max_moves)
+    dev = tour.device
+    tour_out = torch.empty_like(tour)
+    cost_out = torch.empty((B,), dtype=torch.float64, device=dev)
+    moves = torch.zeros((B,), dtype=torch.int32, device=dev)
+    accepted = torch.zeros((B,), dtype=torch.int32, device=dev)
+    status = torch.zeros((B,), dtype=torch.int32, device=dev)
+    trace = torch.full((B, kicks), float("nan"), dtype=torch.float64, device=dev) if want_trace else None
+    f = _or_opt_entry("gnngls_ils_run")
+    _lib.check(f(_lib.ptr(tour.contiguous()), _lib.ptr(cost.contiguous()), _lib.ptr(D.contiguous()), B, n, kicks, kick0, int(max_seg),
+                 int(bool(reverse)), max_moves, ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _lib.ptr(u), _lib.ptr(tour_out),
+                 _lib.ptr(cost_out), _lib.ptr(moves), _lib.ptr(accepted), _lib.ptr(status), _lib.ptr(trace), _lib.current_stream()),
+               "ils_run")
+    return IlsResult(tour_out, cost_out, moves, accepted, status, trace)
+
+
+def ils(tour, cost, D, kicks, max_seg=3, reverse=True, max_moves=None, seed=0, u=None, kick0=0, want_trace=False):
+    """Iterated local search of a batch in one launch: or_opt_descent, then `kicks` times a double-bridge kick of the accepted
+    tour, the same descent from the kicked tour, and the better of the two kept (include/gnngls_hip.h states the cut points,
+    the kick, its delta and the acceptance rule; host.ils restates them in NumPy, bit for bit).  The cut points come from
+    u [B,kicks,3] fp64 uniforms, or (None) from Philox under `seed` with the kick counter starting at kick0: a run that starts
+    from an earlier run's outputs with kick0 = that run's kicks continues it exactly.  max_moves caps the applied descent moves
+    of the whole run (STATUS_MOVE_CAP; None = 100 * n * (kicks + 1), clipped to int32).  kicks = 0 is or_opt_descent.
+    tour [B,n+1] int32, cost [B] fp64, D [B,n,n] fp64 bitwise symmetric, n >= 4 -> IlsResult.  A matrix that is not symmetric
+    raises."""
+    r = ils_launch(tour, cost, D, kicks, max_seg, reverse, max_moves, seed, u, kick0, want_trace)
+    bad = (r.status == STATUS_ASYMMETRIC).nonzero().flatten().tolist()
+    if bad:
+        _raise_asymmetric("ils", bad)
+    return r
+
+
 def gls_run(D, guides, init_tour, init_cost, perturbation_moves=30, first_improvement=False,
             max_outer_iters=-1, time_limit_s=0.0, watchdog_s=None, trace_cap=0, want_trace_time=False,
             want_penalty=False, penalty_bits=0, retry_overflow=True, imp_cap=0, retry_asymmetric=True):

@@ -1,7 +1,7 @@
 """PyTorch-ROCm custom operators of the hot path: `torch.ops.gnngls.*` (north_star).
 
-Ten operators and, since the Or-opt descent, an eleventh are registered with `torch.library` over the C ABI of libgnngls_hip.so
-(include/gnngls_hip.h).  Each has
+Ten operators and, since the Or-opt descent and iterated local search, an eleventh and a twelfth are registered with
+`torch.library` over the C ABI of libgnngls_hip.so (include/gnngls_hip.h).  Each has
 exactly ONE implementation, for the CUDA dispatch key (= HIP on ROCm): there is no CPU kernel behind any of them, so
 calling one with CPU tensors fails in the dispatcher ("no CPU fallback" is structural, not a runtime check).  Shape
 functions (fake/meta kernels) are registered so the ops can be traced and used under FakeTensorMode.  All ops enqueue on
@@ -29,6 +29,10 @@ the current HIP stream, take caller-owned contiguous tensors and retain nothing.
     sample_nn_tours(W[B,n,n] f64, R, depot, invert, seed, u[B,R,n-1] f64 or None) -> (tours[B,R,n+1] i32, status[B,R] i32)
         algorithms.py:21-50, R sampled walks per instance; status 6 (and a tour of -1) marks a walk that met weights which are
         no probabilities -- the op reports, gnngls_amd.ops.sample_nn_tours raises
+    ils(tour, cost[B] f64, D, kicks, kick0, max_seg, reverse, max_moves, seed, u[B,kicks,3] f64 or None) -> (tour, cost,
+        n_moves[B] i32, accepted[B] i32, status[B] i32, trace_cost[B,kicks] f64): iterated local search -- or_opt_descent, then
+        `kicks` double-bridge kicks each followed by the descent, the better tour kept; trace_cost = the candidate's cost after
+        every kick (NaN: never ran); status 3 as for or_opt_descent -- the op reports, gnngls_amd.ops.ils raises
 """
 import ctypes
 
@@ -50,6 +54,8 @@ _LIB.define("one_tree_bound(Tensor D, Tensor ub, int max_iters) -> (Tensor, Tens
 _LIB.define("alpha_nearness(Tensor D, Tensor? pi) -> Tensor")
 _LIB.define("or_opt_descent(Tensor tour, Tensor cost, Tensor D, int max_seg, bool reverse, int max_moves, int trace_cap) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("sample_nn_tours(Tensor W, int R, int depot, bool invert, int seed, Tensor? u) -> (Tensor, Tensor)")
+_LIB.define("ils(Tensor tour, Tensor cost, Tensor D, int kicks, int kick0, int max_seg, bool reverse, int max_moves, int seed, Tensor? u) "
+            "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
 
 _workspaces = {}      # device index -> uint8 scratch tensor for the forward (grown on demand, reused across calls)
 
@@ -126,6 +132,14 @@ _LIB.impl("or_opt_descent", _or_opt_descent, "CUDA")
 _LIB.impl("sample_nn_tours", ops.sample_nn_launch, "CUDA")
 
 
+def _ils(tour, cost, D, kicks, kick0, max_seg, reverse, max_moves, seed, u):
+    r = ops.ils_launch(tour, cost, D, kicks, max_seg, reverse, max_moves, seed, u, kick0, want_trace=True)
+    return r.tour, r.cost, r.moves, r.accepted, r.status, r.trace_cost
+
+
+_LIB.impl("ils", _ils, "CUDA")
+
+
 # ---- shape functions (fake tensors / tracing); no arithmetic -------------------------------------------------------
 @torch.library.register_fake("gnngls::regret_forward")
 def _(feat, packed_weights, n, heads, head_dim, hidden, layers):
@@ -189,3 +203,11 @@ def _(tour, cost, D, max_seg, reverse, max_moves, trace_cap):
 def _(W, R, depot, invert, seed, u):
     B, n = W.shape[0], W.shape[1]
     return W.new_empty((B, R, n + 1), dtype=torch.int32), W.new_empty((B, R), dtype=torch.int32)
+
+
+@torch.library.register_fake("gnngls::ils")
+def _(tour, cost, D, kicks, kick0, max_seg, reverse, max_moves, seed, u):
+    B = tour.shape[0]
+    i32 = lambda: tour.new_empty((B,), dtype=torch.int32)  # noqa: E731
+    return (tour.new_empty(tuple(tour.shape)), cost.new_empty((B,)), i32(), i32(), i32(),
+            cost.new_empty((B, max(int(kicks), 0)), dtype=torch.float64))

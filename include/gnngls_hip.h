@@ -238,6 +238,48 @@ int gnngls_or_opt_descent(const int32_t *tour, const double *cost, const double 
                           int max_moves, int32_t *tour_out, double *cost_out, int32_t *moves, int32_t *status, double *trace_cost,
                           int trace_cap, void *stream);
 
+/* ---- iterated local search: double-bridge kicks around the descent of gnngls_or_opt_descent, one launch -----------------------
+ * The second metaheuristic beside guided local search: kick the local optimum, descend again, keep the better tour.  The
+ * reference has no counterpart.  Definition (the contract; gnngls_amd.host.ils restates it in NumPy, bit for bit):
+ *   tour t[0..n], t[0] = t[n] = the depot, m = n - 1, D [B,n,n] fp64 bitwise symmetric.
+ *   Cut points from three uniforms u0, u1, u2 in [0,1); each product is one fp64 multiply, truncated toward zero, then clamped
+ *   into its range (the device also clamps below at 0; a u outside [0,1) or a NaN still gives a closed permutation -- which one
+ *   is unspecified, as for the sampled walks below):
+ *     p1 = 1 + min(int(u0 * (m - 2)), m - 3)                      1 .. m-2
+ *     p2 = p1 + 1 + min(int(u1 * (m - 1 - p1)), m - 2 - p1)       p1+1 .. m-1
+ *     p3 = p2 + 1 + min(int(u2 * (m - p2)), m - 1 - p2)           p2+1 .. m
+ *   Kick: the orientation-preserving double bridge.  A = t[0:p1], B = t[p1:p2], C = t[p2:p3], Dseg = t[p3:n]; the new tour is
+ *   A + Dseg + C + B + [t[n]] -- A D C B: all four junctions are new (A C B D would only be a segment swap); the depot never
+ *   moves.  With ae = t[p1-1], bs = t[p1], be = t[p2-1], cs = t[p2], ce = t[p3-1], ds = t[p3], de = t[n-1], z = t[n] its delta is,
+ *   fp64, left to right as written, every operation rounded once:
+ *     D[ae,ds] + D[de,cs] + D[ce,bs] + D[be,z] - D[ae,bs] - D[be,cs] - D[ce,ds] - D[de,z]
+ *   Run:
+ *     1. cur, cur_cost = the descent of gnngls_or_opt_descent (max_seg, reverse) from (tour, cost).
+ *     2. for k = 0 .. kicks-1: cand = kick(cur), cand_cost = cur_cost + delta; cand, cand_cost = the same descent from there;
+ *        trace_cost[k] = cand_cost; d = cand_cost - cur_cost; accept iff d < 0 and not np.isclose(0, d) (the reference's
+ *        acceptance rule, operators.py:42, applied to the kick: the accumulated costs of one tour reached by two paths differ in
+ *        their last bits); when accepted cur, cur_cost = cand, cand_cost and accepted += 1.
+ *     3. max_moves caps the applied descent moves of the whole run, checked after every move: the descent in progress ends
+ *        there, step 2's bookkeeping is applied to what it holds, and the run ends with GNNGLS_STATUS_MOVE_CAP.  The loop is
+ *        bounded by kicks and max_moves only: no wall clock, no watchdog, no spin-wait.
+ *   Uniforms: the caller's u [B,kicks,3] fp64, or with u == NULL Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and
+ *   counter (b, kick0 + k, s, 1), s = 0, 1, 2; u = ((o0 << 32 | o1) >> 11) * 2^-53 -- the generator and formula of
+ *   gnngls_sample_nn_tours; counter word 3 = 1 keeps the stream apart from the walks' (b, r, step, 0).
+ *   kick0 >= 0 offsets the kick counter: a run of K1 kicks followed by a run of K2 kicks with kick0 = K1 from the first run's
+ *   outputs IS a run of K1 + K2 kicks (the second run's first descent finds a local optimum and applies nothing) -- a host loop
+ *   runs the search for a time budget in such rounds.  kicks = 0 is exactly gnngls_or_opt_descent.
+ *   Outputs per instance: tour_out [B,n+1]; cost_out [B] the accumulated cost; moves [B] all applied descent moves, the first
+ *   descent's included; accepted [B] accepted kicks; status [B] GNNGLS_STATUS_OK, GNNGLS_STATUS_MOVE_CAP or
+ *   GNNGLS_STATUS_ASYMMETRIC (not searched: the outputs are the inputs); trace_cost [B,kicks] or NULL: entries of kicks that
+ *   never ran stay as given.
+ * One workgroup per instance, one launch for the batch, the tours resident in LDS (the accepted tour in a buffer of its own:
+ * a rejected kick costs no copy).  4 <= n <= GNNGLS_OR_OPT_MAX_N (a larger n returns GNNGLS_ERR_UNSUPPORTED).  Bad arguments --
+ * n < 4, B < 1, kicks < 0, kick0 < 0, kick0 + kicks > INT32_MAX, max_seg outside 1..GNNGLS_OR_OPT_MAX_SEG, max_moves < 1, a NULL
+ * pointer other than u / trace_cost (GNNGLS_ERR_ARG) -- are rejected on the host before any device work. */
+int gnngls_ils_run(const int32_t *tour, const double *cost, const double *D, int B, int n, int kicks, int kick0, int max_seg,
+                   int reverse, int max_moves, uint64_t seed, const double *u, int32_t *tour_out, double *cost_out, int32_t *moves,
+                   int32_t *accepted, int32_t *status, double *trace_cost, void *stream);
+
 /* ---- sampled nearest-neighbour walks (algorithms.py:21-50: probabilistic_nearest_neighbour) ----------------------------------
  * R independent walks per instance, one wavefront each, one launch for the B * R walks.  Walk (b, r):
  *   tour = [depot]; at every step i = tour[-1] and the candidates are the unvisited nodes j in ascending id, g_j = W[b,i,j];
