@@ -37,6 +37,9 @@ SIGNATURES = {
     "gnngls_or_opt_best_move": [_vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp],
     "gnngls_or_opt_descent": [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp],
     "gnngls_ils_run": [_vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gnngls_three_opt_best_move": [_vp, _vp, _int, _int, _vp, _vp, _vp, _vp],
+    "gnngls_three_opt_descent": [_vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp],
+    "gnngls_three_opt_lds_max_n": [],
     "gnngls_sample_nn_tours": [_vp, _int, _int, _int, _int, _int, _u64, _vp, _vp, _vp, _vp],
     "gnngls_gls_run": [_vp, _vp, _int, _int, _int, _vp, _vp, _int, _int, _int, _i64, _f64, _f64,
                        _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp],
@@ -117,6 +120,8 @@ _ALPHA = ("gnngls_alpha_nearness",)
 _OR_OPT = ("gnngls_or_opt_best_move", "gnngls_or_opt_descent")
 # iterated local search (an older build named by GNNGLS_HIP_SO lacks it; ops.ils then raises)
 _ILS = ("gnngls_ils_run",)
+# 3-opt (an older build named by GNNGLS_HIP_SO lacks it; ops.three_opt_best_move / three_opt_descent then raise)
+_THREE_OPT = ("gnngls_three_opt_best_move", "gnngls_three_opt_descent", "gnngls_three_opt_lds_max_n")
 _lib = None
 
 
@@ -139,7 +144,7 @@ def load():
         import torch  # noqa: F401
         L = ctypes.CDLL(SO)
         for name, argtypes in SIGNATURES.items():
-            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS or name in _BOUNDS or name in _SAMPLING or name in _ALPHA or name in _OR_OPT or name in _ILS) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
+            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS or name in _BOUNDS or name in _SAMPLING or name in _ALPHA or name in _OR_OPT or name in _ILS or name in _THREE_OPT) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
                 continue              # an older build of the library named by GNNGLS_HIP_SO (same-box A/B of kernel variants)
             f = getattr(L, name)      # AttributeError if the symbol is missing
             f.argtypes = argtypes

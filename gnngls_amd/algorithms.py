@@ -2,8 +2,9 @@
 `insertion`, `local_search`, `guided_local_search` with the reference's signatures, return values and side
 effects, executed by the HIP kernels (the persistent search kernel, the one-launch insertion constructor).
 `alpha_nearness` (no counterpart in the reference) writes a model-free guide attribute for guided_local_search;
-`or_opt_descent` (no counterpart either) is local_search with Or-opt in relocate's place, and `iterated_local_search` is that
-descent inside a loop of double-bridge kicks.
+`or_opt_descent` (no counterpart either) is local_search with Or-opt in relocate's place, `iterated_local_search` is that
+descent inside a loop of double-bridge kicks, and `three_opt_descent` is local_search with the exhaustive 3-opt scan in relocate's
+place.
 
 The probabilistic constructors (algorithms.py:21-64: `probabilistic_nearest_neighbour`, `best_probabilistic_nearest_neighbour`)
 have the reference's signatures plus a trailing `seed` and the reference's LAW, not its draws: np.random.choice draws from NumPy's
@@ -165,6 +166,19 @@ def or_opt_descent(init_tour, init_cost, D, max_seg=3, reverse=True):
                            ops.as_dev(np.asarray([init_cost], dtype=np.float64), torch.float64),
                            ops.as_dev(np.asarray(D, dtype=np.float64)[None], torch.float64), max_seg, reverse)
     return r.tour[0].tolist(), r.cost[0].item(), int(r.moves[0])
+
+
+def three_opt_descent(init_tour, init_cost, D):
+    """local_search above with relocate_a2a replaced by the exhaustive 3-opt scan (operators.three_opt_a2a), best improvement, on
+    the GPU (ops.three_opt_descent; no counterpart in the reference) -> (tour, cost, search_progress): one {'time', 'cost'} per
+    applied move as local_search records them, every 'time' the moment the launch returned (the kernel keeps no clock)."""
+    n = len(init_tour) - 1
+    r = ops.three_opt_descent(ops.as_dev(np.asarray(init_tour, dtype=np.int32)[None], torch.int32),
+                              ops.as_dev(np.asarray([init_cost], dtype=np.float64), torch.float64),
+                              ops.as_dev(np.asarray(D, dtype=np.float64)[None], torch.float64), trace_cap=100 * n)
+    moves = int(r.moves[0])
+    t = time.time()
+    return r.tour[0].tolist(), r.cost[0].item(), [{"time": t, "cost": c} for c in r.trace_cost[0, :moves].tolist()]
 
 
 def iterated_local_search(init_tour, init_cost, D, kicks, max_seg=3, reverse=True, seed=None):

@@ -23,6 +23,7 @@
 #include "model_plan.h"
 #include "oropt_kernels.h"
 #include "sampling_kernels.h"
+#include "threeopt_kernels.h"
 #include "train_kernels.h"
 
 namespace {
@@ -337,6 +338,44 @@ int gnngls_ils_run(const int32_t *tour, const double *cost, const double *D, int
                                       accepted, status, trace_cost, (hipStream_t)stream);
     return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "ils_run");
 }
+
+static_assert(GNNGLS_THREE_OPT_MAX_N == gnngls::kThreeOptMaxN && GNNGLS_STATUS_ASYMMETRIC == gnngls::kThreeOptStatusAsymmetric &&
+              GNNGLS_STATUS_MOVE_CAP == gnngls::kThreeOptStatusMoveCap, "include/gnngls_hip.h and threeopt_kernels.h disagree");
+
+// the checks both 3-opt entries share; 0 = the arguments are fine
+static int three_opt_args(const char *what, int B, int n) {
+    if (B < 1) return fail(GNNGLS_ERR_ARG, "%s: B=%d must be >= 1", what, B);
+    if (n < 3) return fail(GNNGLS_ERR_ARG, "%s: n=%d must be >= 3", what, n);
+    if (n > GNNGLS_THREE_OPT_MAX_N)
+        return fail(GNNGLS_ERR_UNSUPPORTED, "%s: n=%d exceeds the largest supported instance (n <= %d: a move's selection key holds "
+                    "its positions in eight bits each)", what, n, GNNGLS_THREE_OPT_MAX_N);
+    return GNNGLS_OK;
+}
+
+int gnngls_three_opt_best_move(const int32_t *tour, const double *D, int B, int n, double *delta, int32_t *move, int32_t *new_tour,
+                               void *stream) {
+    if (int rc = three_opt_args("three_opt_best_move", B, n)) return rc;
+    if (!tour || !D || !delta || !move || !new_tour)
+        return fail(GNNGLS_ERR_ARG, "three_opt_best_move: NULL pointer (tour, D, delta, move, new_tour)");
+    hipError_t e = gnngls::launch_three_opt_best_move(tour, D, B, n, delta, move, new_tour, (hipStream_t)stream);
+    return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "three_opt_best_move");
+}
+
+int gnngls_three_opt_descent(const int32_t *tour, const double *cost, const double *D, int B, int n, int max_moves, int32_t *tour_out,
+                             double *cost_out, int32_t *moves, int32_t *status, double *trace_cost, int trace_cap, void *stream) {
+    if (int rc = three_opt_args("three_opt_descent", B, n)) return rc;
+    if (max_moves < 1) return fail(GNNGLS_ERR_ARG, "three_opt_descent: max_moves=%d must be >= 1 (it bounds the loop)", max_moves);
+    if (trace_cap < 0) return fail(GNNGLS_ERR_ARG, "three_opt_descent: trace_cap=%d must be >= 0", trace_cap);
+    if (!tour || !cost || !D || !tour_out || !cost_out || !moves || !status)
+        return fail(GNNGLS_ERR_ARG, "three_opt_descent: NULL pointer (tour, cost, D, tour_out, cost_out, moves, status)");
+    if (!trace_cost && trace_cap > 0)
+        return fail(GNNGLS_ERR_ARG, "three_opt_descent: NULL pointer (trace_cost) with trace_cap=%d (NULL only with trace_cap 0)", trace_cap);
+    hipError_t e = gnngls::launch_three_opt_descent(tour, cost, D, B, n, max_moves, tour_out, cost_out, moves, status, trace_cost,
+                                                    trace_cap, (hipStream_t)stream);
+    return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "three_opt_descent");
+}
+
+int gnngls_three_opt_lds_max_n(void) { return gnngls::three_opt_lds_max_n(); }
 
 static_assert(GNNGLS_SAMPLE_MAX_N == gnngls::kSampleMaxN && GNNGLS_SAMPLE_BAD_WEIGHTS == GNNGLS_SAMPLE_BAD_WEIGHTS_DEV,
               "include/gnngls_hip.h and sampling_kernels.h disagree");

@@ -214,6 +214,93 @@ def or_opt_descent(tour, cost, D, max_seg=3, reverse=True, max_moves=None):
     return tour, cost, len(trace), trace
 
 
+def three_opt_cost(tour, D, p1, p2, p3, kind):
+    """The delta of the 3-opt candidate (p1, p2, p3, kind) (include/gnngls_hip.h states the definition): the tour edges at
+    positions p1 < p2 < p3 leave, the pieces B = tour[p1+1..p2] and C = tour[p2+1..p3] are reconnected between the head and the
+    tail in the way `kind` names.  fp64, left to right as written: the three added edges in the table's order, then the three
+    removed ones."""
+    n = len(tour) - 1
+    assert 0 <= p1 < p2 < p3 <= n - 1 and kind in (0, 1, 2, 3)
+    a1, b1, b2, c1, c2, a2 = tour[p1], tour[p1 + 1], tour[p2], tour[p2 + 1], tour[p3], tour[p3 + 1]
+    if kind == 0:
+        x, y, z = D[a1, b2], D[b1, c2], D[c1, a2]
+    elif kind == 1:
+        x, y, z = D[a1, c1], D[c2, b1], D[b2, a2]
+    elif kind == 2:
+        x, y, z = D[a1, c2], D[c1, b1], D[b2, a2]
+    else:
+        x, y, z = D[a1, c1], D[c2, b2], D[b1, a2]
+    return x + y + z - D[a1, b1] - D[b2, c1] - D[c2, a2]
+
+
+def three_opt(tour, p1, p2, p3, kind):
+    """The tour after the 3-opt move: H + (B reversed + C reversed | C + B | C reversed + B | C + B reversed) + T for kind 0..3,
+    H = tour[0..p1], B = tour[p1+1..p2], C = tour[p2+1..p3], T = tour[p3+1..n]: the depot never moves."""
+    tour = list(tour)
+    H, B, C, T = tour[:p1 + 1], tour[p1 + 1:p2 + 1], tour[p2 + 1:p3 + 1], tour[p3 + 1:]
+    mid = (B[::-1] + C[::-1], C + B, C[::-1] + B, C + B[::-1])[kind]
+    return H + mid + T
+
+
+def three_opt_a2a(tour, D):
+    """One best-improvement scan of the 3-opt neighbourhood: every candidate (p1, p2, p3, kind) in ascending lexicographic order,
+    the reference's rule `delta < best_delta and not np.isclose(0, delta)` -- the first candidate with the smallest qualifying
+    delta.  -> (delta, (p1, p2, p3, kind)) or (0, None).  Vectorised per p1 over (p2, p3, kind) with the operand order of
+    three_opt_cost."""
+    import numpy as np
+    t = np.asarray(tour)
+    n = len(t) - 1
+    D = np.asarray(D, dtype=np.float64)
+    M = D[t[:, None], t[None, :]]                         # M[p, q] = D[tour[p], tour[q]]
+    e = M[np.arange(n), np.arange(1, n + 1)]              # the tour edge at position p
+    best = None                                           # (delta, p1, p2, p3, kind)
+    for p1 in range(0, n - 2):
+        p2 = np.arange(p1 + 1, n - 1)[:, None]
+        p3 = np.arange(p1 + 2, n)[None, :]
+        x = np.stack(np.broadcast_arrays(M[p1, p2], M[p1, p2 + 1], M[p1, p3], M[p1, p2 + 1]), axis=-1)
+        y = np.stack(np.broadcast_arrays(M[p1 + 1, p3], M[p3, p1 + 1], M[p2 + 1, p1 + 1], M[p3, p2]), axis=-1)
+        z = np.stack(np.broadcast_arrays(M[p2 + 1, p3 + 1], M[p2, p3 + 1], M[p2, p3 + 1], M[p1 + 1, p3 + 1]), axis=-1)
+        delta = x + y + z - e[p1] - e[p2][..., None] - e[p3][..., None]
+        ok = (p3 > p2)[..., None] & (delta < 0) & ~_isclose0(delta)
+        if not ok.any():
+            continue
+        m = delta[ok].min()
+        r, col, kind = np.argwhere(ok & (delta == m))[0]  # row-major: the first (p2, p3, kind) of this p1
+        cand = (m, p1, int(r) + p1 + 1, int(col) + p1 + 2, int(kind))
+        if best is None or cand[0] < best[0]:
+            best = cand
+    if best is None:
+        return 0, None
+    return best[0], best[1:]
+
+
+def three_opt_descent(tour, cost, D, max_moves=None):
+    """The reference's local_search (algorithms.py:111-132), best improvement, with relocate_a2a replaced by three_opt_a2a:
+    two_opt_a2a and three_opt_a2a alternate, cost += delta after each move, until a full pass moves nothing or max_moves moves are
+    applied (checked after every move; None: no cap).  -> (tour, cost, moves, cost_trace): the definition that
+    gnngls_amd.ops.three_opt_descent is compared against bit for bit."""
+    tour = [int(v) for v in tour]
+    trace = []
+    improved = True
+    while improved:
+        improved = False
+        for op in (0, 1):
+            delta, move = two_opt_a2a(tour, D) if op == 0 else three_opt_a2a(tour, D)
+            if move is None:
+                continue
+            if op == 0:
+                i, j = move
+                tour = tour[:i] + tour[j - 1:i - 1:-1] + tour[j:]      # operators.py:11
+            else:
+                tour = three_opt(tour, *move)
+            cost = cost + delta
+            trace.append(cost)
+            improved = True
+            if max_moves is not None and len(trace) >= max_moves:
+                return tour, cost, len(trace), trace
+    return tour, cost, len(trace), trace
+
+
 def double_bridge_cuts(u, n):
     """The cut points (p1, p2, p3) of a double-bridge kick from three uniforms in [0,1), 1 <= p1 < p2 < p3 <= n-1, n >= 4
     (include/gnngls_hip.h states the definition): with m = n - 1 each product is one fp64 multiply, truncated toward zero, then

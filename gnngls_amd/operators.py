@@ -110,3 +110,29 @@ def or_opt_a2a(tour, D, max_seg=3, reverse=True):
     if mv[0] < 0:
         return 0, tour
     return delta.item(), or_opt(tour, *mv)
+
+
+def three_opt(tour, p1, p2, p3, kind):
+    """The 3-opt move (no counterpart in the reference): the tour edges at positions p1 < p2 < p3 leave, and B = tour[p1+1..p2]
+    and C = tour[p2+1..p3] come back between the head and the tail as B reversed + C reversed (kind 0), C + B (1), C reversed + B
+    (2) or C + B reversed (3)."""
+    H, B, C, T = tour[:p1 + 1], tour[p1 + 1:p2 + 1], tour[p2 + 1:p3 + 1], tour[p3 + 1:]
+    return H + (B[::-1] + C[::-1], C + B, C[::-1] + B, C + B[::-1])[kind] + T
+
+
+def three_opt_cost(tour, D, p1, p2, p3, kind):
+    """The delta of the candidate (p1, p2, p3, kind) as include/gnngls_hip.h defines it.  Six matrix entries: evaluated on the host
+    by gnngls_amd.host.three_opt_cost, the definition the kernels are tested against; the scan below runs on the GPU."""
+    from . import host
+    return float(host.three_opt_cost(tour, np.asarray(D, dtype=np.float64), p1, p2, p3, kind))
+
+
+def three_opt_a2a(tour, D):
+    """One best-improvement scan of the 3-opt neighbourhood (all C(n,3) x 4 candidates) in the style of two_opt_a2a
+    (operators.py:32-50): -> (delta, new_tour), (0, tour) when nothing qualifies."""
+    t, d = _dev(tour, D)
+    delta, move, _ = ops.three_opt_best_move(t, d)
+    mv = move[0].tolist()
+    if mv[0] < 0:
+        return 0, tour
+    return delta.item(), three_opt(tour, *mv)

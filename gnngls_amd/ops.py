@@ -338,9 +338,8 @@ def _or_opt_entry(name):
     return getattr(L, name)
 
 
-def _raise_asymmetric(what, bad):
-    raise ValueError(f"{what}: the matrices of instances {bad[:8]} are not bitwise symmetric (status {STATUS_ASYMMETRIC}): "
-                     "the Or-opt kernels read D[d,s] as D[s][d]")
+def _raise_asymmetric(what, bad, why="the Or-opt kernels read D[d,s] as D[s][d]"):
+    raise ValueError(f"{what}: the matrices of instances {bad[:8]} are not bitwise symmetric (status {STATUS_ASYMMETRIC}): {why}")
 
 
 def or_opt_best_move(tour, D, max_seg=3, reverse=True):
@@ -392,6 +391,80 @@ def or_opt_descent(tour, cost, D, max_seg=3, reverse=True, max_moves=None, trace
     bad = (r.status == STATUS_ASYMMETRIC).nonzero().flatten().tolist()
     if bad:
         _raise_asymmetric("or_opt_descent", bad)
+    return r
+
+
+THREE_OPT_MAX_N = 256                                         # GNNGLS_THREE_OPT_MAX_N
+
+
+@dataclass
+class ThreeOptResult:
+    tour: torch.Tensor           # [B,n+1] int32
+    cost: torch.Tensor           # [B] fp64: the start cost plus the deltas of the applied moves, in order
+    moves: torch.Tensor          # [B] int32 applied moves (2-opt and 3-opt)
+    status: torch.Tensor         # [B] int32 STATUS_OK (a local optimum of both scans) or STATUS_MOVE_CAP
+    trace_cost: torch.Tensor     # [B,trace_cap] fp64 the cost after each of the first trace_cap moves, or None
+
+
+_THREE_OPT_READS = "the 3-opt kernels read D[c2,b1] as D[b1][c2]"
+
+
+def three_opt_lds_max_n():
+    """The largest n whose distance triangle the 3-opt kernels of this build stage in LDS; larger instances read D from global
+    memory (the results are the same bit for bit)."""
+    return int(_or_opt_entry("gnngls_three_opt_lds_max_n")())
+
+
+def three_opt_best_move(tour, D):
+    """One best-improvement scan of the 3-opt neighbourhood of every tour of a batch, one launch: the tour edges at positions
+    p1 < p2 < p3 leave and the pieces between them are reconnected in the four ways that are no 2-opt move, all C(n,3) x 4
+    candidates (include/gnngls_hip.h states the candidates, the delta and the order; host.three_opt_a2a restates them in NumPy, bit
+    for bit).  tour [B,n+1] int32, D [B,n,n] fp64 bitwise symmetric, 3 <= n <= THREE_OPT_MAX_N -> (delta [B] fp64, 0.0 when nothing
+    qualifies; move [B,4] int32 = p1, p2, p3, kind, -1s when none; new_tour [B,n+1] int32).  A matrix that is not symmetric
+    raises."""
+    B, n = _check_shapes(tour, D)
+    delta = torch.empty((B,), dtype=torch.float64, device=tour.device)
+    move = torch.empty((B, 4), dtype=torch.int32, device=tour.device)
+    new_tour = torch.empty_like(tour)
+    f = _or_opt_entry("gnngls_three_opt_best_move")
+    _lib.check(f(_lib.ptr(tour.contiguous()), _lib.ptr(D.contiguous()), B, n, _lib.ptr(delta), _lib.ptr(move), _lib.ptr(new_tour),
+                 _lib.current_stream()), "three_opt_best_move")
+    bad = torch.isnan(delta).nonzero().flatten().tolist()
+    if bad:
+        _raise_asymmetric("three_opt_best_move", bad, _THREE_OPT_READS)
+    return delta, move, new_tour
+
+
+def three_opt_launch(tour, cost, D, max_moves=None, trace_cap=0):
+    """The launch behind three_opt_descent and torch.ops.gnngls.three_opt_descent: -> ThreeOptResult, nothing raised for an
+    instance whose matrix is not symmetric (its status is STATUS_ASYMMETRIC, its outputs are its inputs)."""
+    B, n = _check_shapes(tour, D)
+    assert cost.dtype == torch.float64 and cost.shape == (B,), f"cost shape {tuple(cost.shape)} is not [{B}]"
+    max_moves = 100 * n if max_moves is None else int(max_moves)
+    trace_cap = int(trace_cap)
+    dev = tour.device
+    tour_out = torch.empty_like(tour)
+    cost_out = torch.empty((B,), dtype=torch.float64, device=dev)
+    moves = torch.zeros((B,), dtype=torch.int32, device=dev)
+    status = torch.zeros((B,), dtype=torch.int32, device=dev)
+    trace = torch.zeros((B, trace_cap), dtype=torch.float64, device=dev) if trace_cap > 0 else None
+    f = _or_opt_entry("gnngls_three_opt_descent")
+    _lib.check(f(_lib.ptr(tour.contiguous()), _lib.ptr(cost.contiguous()), _lib.ptr(D.contiguous()), B, n, max_moves,
+                 _lib.ptr(tour_out), _lib.ptr(cost_out), _lib.ptr(moves), _lib.ptr(status), _lib.ptr(trace), trace_cap,
+                 _lib.current_stream()), "three_opt_descent")
+    return ThreeOptResult(tour_out, cost_out, moves, status, trace)
+
+
+def three_opt_descent(tour, cost, D, max_moves=None, trace_cap=0):
+    """The reference's local_search (algorithms.py:111-132) with relocate_a2a replaced by the 3-opt scan of three_opt_best_move:
+    two_opt_a2a and the 3-opt scan alternate, best improvement, cost += delta after each move, until a full pass moves nothing
+    (status STATUS_OK) or max_moves moves are applied (STATUS_MOVE_CAP; None = 100 * n).  One launch for the batch, bit for bit
+    host.three_opt_descent.  tour [B,n+1] int32, cost [B] fp64, D [B,n,n] fp64 bitwise symmetric, 3 <= n <= THREE_OPT_MAX_N
+    -> ThreeOptResult.  A matrix that is not symmetric raises."""
+    r = three_opt_launch(tour, cost, D, max_moves, trace_cap)
+    bad = (r.status == STATUS_ASYMMETRIC).nonzero().flatten().tolist()
+    if bad:
+        _raise_asymmetric("three_opt_descent", bad, _THREE_OPT_READS)
     return r
 
 

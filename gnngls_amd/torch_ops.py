@@ -1,6 +1,7 @@
 """PyTorch-ROCm custom operators of the hot path: `torch.ops.gnngls.*` (north_star).
 
-Ten operators and, since the Or-opt descent and iterated local search, an eleventh and a twelfth are registered with
+Ten operators and, since the Or-opt descent, iterated local search and the 3-opt descent, an eleventh, a twelfth and a thirteenth
+are registered with
 `torch.library` over the C ABI of libgnngls_hip.so (include/gnngls_hip.h).  Each has
 exactly ONE implementation, for the CUDA dispatch key (= HIP on ROCm): there is no CPU kernel behind any of them, so
 calling one with CPU tensors fails in the dispatcher ("no CPU fallback" is structural, not a runtime check).  Shape
@@ -33,6 +34,9 @@ the current HIP stream, take caller-owned contiguous tensors and retain nothing.
         n_moves[B] i32, accepted[B] i32, status[B] i32, trace_cost[B,kicks] f64): iterated local search -- or_opt_descent, then
         `kicks` double-bridge kicks each followed by the descent, the better tour kept; trace_cost = the candidate's cost after
         every kick (NaN: never ran); status 3 as for or_opt_descent -- the op reports, gnngls_amd.ops.ils raises
+    three_opt_descent(tour, cost[B] f64, D, max_moves, trace_capacity) -> (tour, cost, n_moves[B] i32, status[B] i32,
+        trace_cost[B,trace_capacity] f64): local_search with the exhaustive 3-opt scan in relocate's place, n <= 256; status 3 as
+        for or_opt_descent -- the op reports, gnngls_amd.ops.three_opt_descent raises
 """
 import ctypes
 
@@ -56,6 +60,7 @@ _LIB.define("or_opt_descent(Tensor tour, Tensor cost, Tensor D, int max_seg, boo
 _LIB.define("sample_nn_tours(Tensor W, int R, int depot, bool invert, int seed, Tensor? u) -> (Tensor, Tensor)")
 _LIB.define("ils(Tensor tour, Tensor cost, Tensor D, int kicks, int kick0, int max_seg, bool reverse, int max_moves, int seed, Tensor? u) "
             "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+_LIB.define("three_opt_descent(Tensor tour, Tensor cost, Tensor D, int max_moves, int trace_capacity) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
 
 _workspaces = {}      # device index -> uint8 scratch tensor for the forward (grown on demand, reused across calls)
 
@@ -140,6 +145,15 @@ def _ils(tour, cost, D, kicks, kick0, max_seg, reverse, max_moves, seed, u):
 _LIB.impl("ils", _ils, "CUDA")
 
 
+def _three_opt_descent(tour, cost, D, max_moves, trace_capacity):
+    r = ops.three_opt_launch(tour, cost, D, max_moves, trace_capacity)
+    trace = r.trace_cost if r.trace_cost is not None else torch.zeros((tour.shape[0], 0), dtype=torch.float64, device=tour.device)
+    return r.tour, r.cost, r.moves, r.status, trace
+
+
+_LIB.impl("three_opt_descent", _three_opt_descent, "CUDA")
+
+
 # ---- shape functions (fake tensors / tracing); no arithmetic -------------------------------------------------------
 @torch.library.register_fake("gnngls::regret_forward")
 def _(feat, packed_weights, n, heads, head_dim, hidden, layers):
@@ -211,3 +225,11 @@ def _(tour, cost, D, kicks, kick0, max_seg, reverse, max_moves, seed, u):
     i32 = lambda: tour.new_empty((B,), dtype=torch.int32)  # noqa: E731
     return (tour.new_empty(tuple(tour.shape)), cost.new_empty((B,)), i32(), i32(), i32(),
             cost.new_empty((B, max(int(kicks), 0)), dtype=torch.float64))
+
+
+@torch.library.register_fake("gnngls::three_opt_descent")
+def _(tour, cost, D, max_moves, trace_capacity):
+    B = tour.shape[0]
+    i32 = lambda: tour.new_empty((B,), dtype=torch.int32)  # noqa: E731
+    return (tour.new_empty(tuple(tour.shape)), cost.new_empty((B,)), i32(), i32(),
+            cost.new_empty((B, max(int(trace_capacity), 0)), dtype=torch.float64))

@@ -280,6 +280,52 @@ int gnngls_ils_run(const int32_t *tour, const double *cost, const double *D, int
                    int reverse, int max_moves, uint64_t seed, const double *u, int32_t *tour_out, double *cost_out, int32_t *moves,
                    int32_t *accepted, int32_t *status, double *trace_cost, void *stream);
 
+/* ---- 3-opt: three tour edges leave and the pieces between them are reconnected in every way that is no 2-opt move -------------
+ * The upper end of the classical family beside 2-opt, relocate and Or-opt: every Or-opt candidate above, with any max_seg and
+ * reversed or not, is a 3-opt move of the same tour.  The reference has no counterpart.  Definition (the contract;
+ * gnngls_amd.host restates it in NumPy, bit for bit):
+ *   tour t[0..n], t[0] = t[n] = the depot.  The tour edge at position p is (t[p], t[p+1]), p = 0..n-1.  A candidate is
+ *   (p1, p2, p3, kind) with 0 <= p1 < p2 < p3 <= n-1 and kind in 0..3.  Removing the three edges leaves the head H = t[0..p1],
+ *   B = t[p1+1..p2], C = t[p2+1..p3] and the tail T = t[p3+1..n]; head and tail stay, so the depot never moves.
+ *   a1 = t[p1], b1 = t[p1+1], b2 = t[p2], c1 = t[p2+1], c2 = t[p3], a2 = t[p3+1].
+ *     kind 0:  H + B reversed + C reversed + T    added edges, in this order: D[a1,b2], D[b1,c2], D[c1,a2]
+ *     kind 1:  H + C + B + T                                                  D[a1,c1], D[c2,b1], D[b2,a2]
+ *     kind 2:  H + C reversed + B + T                                         D[a1,c2], D[c1,b1], D[b2,a2]
+ *     kind 3:  H + C + B reversed + T                                         D[a1,c1], D[c2,b2], D[b1,a2]
+ *   delta, fp64, evaluated left to right exactly as written, every operation rounded once, with x, y, z the kind's added edges:
+ *     delta = ((((x + y) + z) - D[a1,b1]) - D[b2,c1]) - D[c2,a2]
+ *   Degenerate candidates (|B| = 1 or |C| = 1: a kind reproduces a 2-opt tour or another kind's tour) stay in the enumeration:
+ *   they are valid tours and the tie rule decides between them.
+ *   Acceptance is the reference's: delta < best_delta and not np.isclose(0, delta) (operators.py:42).  Candidates are enumerated
+ *   in ascending lexicographic order of (p1, p2, p3, kind); the chosen move is the first candidate with the smallest qualifying
+ *   delta.  Nothing is pruned: a scan evaluates all C(n,3) x 4 candidates.
+ *   D [B,n,n] must be bitwise symmetric (the kernels read D[c2,b1] as D[b1][c2]; one pass in front of the first scan checks it);
+ *   tour entries are node ids in 0..n-1 (the kernels clamp nothing).
+ * gnngls_three_opt_best_move: one scan.  delta [B] = the chosen move's delta, 0.0 when no candidate qualifies, NaN for an
+ *   instance whose matrix is not bitwise symmetric; move [B,4] = p1, p2, p3, kind (-1s when none); new_tour [B,n+1] = the tour
+ *   after the move (the input when none).
+ * gnngls_three_opt_descent: local_search (algorithms.py:111-132) with relocate_a2a replaced by the scan above -- two_opt_a2a
+ *   (operators.py:32-50) and the 3-opt scan alternate, best improvement; after each move cost += delta; the loop ends when a
+ *   full pass moves nothing, or after max_moves applied moves (checked after every move).
+ *   tour [B,n+1], cost [B] the start tours and their lengths; tour_out, cost_out the result; moves [B] applied moves;
+ *   trace_cost [B,trace_cap] (NULL only with trace_cap 0): the cost after each of the first trace_cap moves (later entries
+ *   untouched).
+ *   status [B]: GNNGLS_STATUS_OK (a local optimum of both scans), GNNGLS_STATUS_MOVE_CAP (the cap ended the run, even where
+ *   the tour happens to be a local optimum), or GNNGLS_STATUS_ASYMMETRIC (not searched: the outputs are the inputs, 0 moves).
+ *   A NaN fails every comparison of the acceptance rule, so an instance with NaN costs stops at once.
+ * One workgroup per instance, one launch for the batch; the loop is bounded by max_moves: no watchdog, no wall clock.
+ * 3 <= n <= GNNGLS_THREE_OPT_MAX_N (a position takes eight bits of the selection key, and one workgroup's O(n^3) scan is of no
+ * use beyond it; a larger n returns GNNGLS_ERR_UNSUPPORTED; n = 3 has one triple and never moves).  Bad arguments -- a NULL
+ * pointer (trace_cost: with trace_cap > 0), B < 1, n < 3, max_moves < 1, trace_cap < 0 (GNNGLS_ERR_ARG) -- are rejected on the
+ * host before any device work.  gnngls_three_opt_lds_max_n: the largest n whose distance triangle this build stages in LDS
+ * (larger instances read D from global memory; the results are the same bit for bit). */
+#define GNNGLS_THREE_OPT_MAX_N 256
+int gnngls_three_opt_best_move(const int32_t *tour, const double *D, int B, int n, double *delta, int32_t *move, int32_t *new_tour,
+                               void *stream);
+int gnngls_three_opt_descent(const int32_t *tour, const double *cost, const double *D, int B, int n, int max_moves, int32_t *tour_out,
+                             double *cost_out, int32_t *moves, int32_t *status, double *trace_cost, int trace_cap, void *stream);
+int gnngls_three_opt_lds_max_n(void);
+
 /* ---- sampled nearest-neighbour walks (algorithms.py:21-50: probabilistic_nearest_neighbour) ----------------------------------
  * R independent walks per instance, one wavefront each, one launch for the B * R walks.  Walk (b, r):
  *   tour = [depot]; at every step i = tour[-1] and the candidates are the unvisited nodes j in ascending id, g_j = W[b,i,j];
