@@ -37,6 +37,9 @@ SIGNATURES = {
     "gnngls_or_opt_best_move": [_vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp],
     "gnngls_or_opt_descent": [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp],
     "gnngls_ils_run": [_vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gnngls_or_opt_o2a": [_vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp],
+    "gnngls_guided_or_opt_run": [_vp, _vp, _vp, _vp, _int, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _int, _int,
+                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp],
     "gnngls_three_opt_best_move": [_vp, _vp, _int, _int, _vp, _vp, _vp, _vp],
     "gnngls_three_opt_descent": [_vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp],
     "gnngls_three_opt_lds_max_n": [],
@@ -122,6 +125,8 @@ _OR_OPT = ("gnngls_or_opt_best_move", "gnngls_or_opt_descent")
 _ILS = ("gnngls_ils_run",)
 # 3-opt (an older build named by GNNGLS_HIP_SO lacks it; ops.three_opt_best_move / three_opt_descent then raise)
 _THREE_OPT = ("gnngls_three_opt_best_move", "gnngls_three_opt_descent", "gnngls_three_opt_lds_max_n")
+# guided local search over 2-opt and Or-opt (an older build named by GNNGLS_HIP_SO lacks it; ops.or_opt_o2a / guided_or_opt then raise)
+_GUIDED_OR_OPT = ("gnngls_or_opt_o2a", "gnngls_guided_or_opt_run")
 _lib = None
 
 
@@ -144,7 +149,7 @@ def load():
         import torch  # noqa: F401
         L = ctypes.CDLL(SO)
         for name, argtypes in SIGNATURES.items():
-            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS or name in _BOUNDS or name in _SAMPLING or name in _ALPHA or name in _OR_OPT or name in _ILS or name in _THREE_OPT) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
+            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS or name in _BOUNDS or name in _SAMPLING or name in _ALPHA or name in _OR_OPT or name in _ILS or name in _THREE_OPT or name in _GUIDED_OR_OPT) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
                 continue              # an older build of the library named by GNNGLS_HIP_SO (same-box A/B of kernel variants)
             f = getattr(L, name)      # AttributeError if the symbol is missing
             f.argtypes = argtypes

@@ -339,6 +339,47 @@ int gnngls_ils_run(const int32_t *tour, const double *cost, const double *D, int
     return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "ils_run");
 }
 
+static_assert(GNNGLS_STATUS_STEP_CAP == gnngls::kGuidedStatusStepCap, "include/gnngls_hip.h and oropt_kernels.h disagree");
+
+int gnngls_or_opt_o2a(const int32_t *tour, const double *D, const int32_t *pos, int B, int n, int max_seg, int reverse, double *delta,
+                      int32_t *move, int32_t *new_tour, void *stream) {
+    if (int rc = or_opt_args("or_opt_o2a", B, n, max_seg)) return rc;
+    if (!tour || !D || !pos || !delta || !move || !new_tour)
+        return fail(GNNGLS_ERR_ARG, "or_opt_o2a: NULL pointer (tour, D, pos, delta, move, new_tour)");
+    hipError_t e = gnngls::launch_or_opt_o2a(tour, D, pos, B, n, max_seg, reverse, delta, move, new_tour, (hipStream_t)stream);
+    return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "or_opt_o2a");
+}
+
+int gnngls_guided_or_opt_run(const int32_t *tour, const double *cost, const double *D, const double *guides, int G, const double *k,
+                             int32_t *penalty, int B, int n, int outer_iters, int iter0, int perturbation_moves, int max_seg,
+                             int reverse, int max_moves, int max_steps, int32_t *tour_out, double *cost_out, int32_t *best_tour,
+                             double *best_cost, int32_t *moves, int32_t *steps, int32_t *status, double *trace_cost, int trace_cap,
+                             int32_t *trace_len, void *stream) {
+    if (n < 4) return fail(GNNGLS_ERR_ARG, "guided_or_opt_run: n=%d must be >= 4", n);
+    if (int rc = or_opt_args("guided_or_opt_run", B, n, max_seg)) return rc;
+    if (outer_iters < 0) return fail(GNNGLS_ERR_ARG, "guided_or_opt_run: outer_iters=%d must be >= 0", outer_iters);
+    if (iter0 < 0) return fail(GNNGLS_ERR_ARG, "guided_or_opt_run: iter0=%d must be >= 0", iter0);
+    if ((long long)iter0 + outer_iters > 0x7fffffffLL)
+        return fail(GNNGLS_ERR_ARG, "guided_or_opt_run: iter0 + outer_iters = %lld exceeds 2^31 - 1 (the guide index)",
+                    (long long)iter0 + outer_iters);
+    if (outer_iters > 0 && (G < 1 || !guides))
+        return fail(GNNGLS_ERR_ARG, "guided_or_opt_run: outer_iters=%d needs guides (G=%d, guides %s)", outer_iters, G,
+                    guides ? "given" : "NULL");
+    if (perturbation_moves < 0)
+        return fail(GNNGLS_ERR_ARG, "guided_or_opt_run: perturbation_moves=%d must be >= 0", perturbation_moves);
+    if (max_moves < 1) return fail(GNNGLS_ERR_ARG, "guided_or_opt_run: max_moves=%d must be >= 1 (it bounds the run)", max_moves);
+    if (max_steps < 1) return fail(GNNGLS_ERR_ARG, "guided_or_opt_run: max_steps=%d must be >= 1 (it bounds the run)", max_steps);
+    if (trace_cap < 0) return fail(GNNGLS_ERR_ARG, "guided_or_opt_run: trace_cap=%d must be >= 0", trace_cap);
+    if (!tour || !cost || !D || !k || !penalty || !tour_out || !cost_out || !best_tour || !best_cost || !moves || !steps || !status)
+        return fail(GNNGLS_ERR_ARG, "guided_or_opt_run: NULL pointer (tour, cost, D, k, penalty, tour_out, cost_out, best_tour, "
+                    "best_cost, moves, steps, status)");
+    hipError_t e = gnngls::launch_guided_or_opt(tour, cost, D, guides, G > 0 ? G : 1, k, penalty, B, n, outer_iters, iter0,
+                                                perturbation_moves, max_seg, reverse, max_moves, max_steps, tour_out, cost_out,
+                                                best_tour, best_cost, moves, steps, status, trace_cost, trace_cost ? trace_cap : 0,
+                                                trace_len, (hipStream_t)stream);
+    return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "guided_or_opt_run");
+}
+
 static_assert(GNNGLS_THREE_OPT_MAX_N == gnngls::kThreeOptMaxN && GNNGLS_STATUS_ASYMMETRIC == gnngls::kThreeOptStatusAsymmetric &&
               GNNGLS_STATUS_MOVE_CAP == gnngls::kThreeOptStatusMoveCap, "include/gnngls_hip.h and threeopt_kernels.h disagree");
 

@@ -347,6 +347,248 @@ __global__ __launch_bounds__(kWave *kOrOptWaves) void ils_kernel(const int32_t *
     if (tid == 0) { cost_out[b] = acc_cost; moves_out[b] = moves; accepted_out[b] = accepted; status_out[b] = status; }
 }
 
+// ---- guided local search over 2-opt and Or-opt (guided_or_opt_kernel) and the one-to-all scans it is made of -----------------
+// The reference's guided_local_search (algorithms.py:135-195) around the descent above: a penalty step picks the tour edge of
+// the greatest utility, counts it in the penalty matrix (global memory, int32, both orientations) and runs the one-to-all scans
+// of two_opt_o2a and of the Or-opt chains that contain the endpoint on Dg = D + k * penalty.  An entry of Dg is one gather of D,
+// one of the penalty, one multiply and one add (contraction is off in this unit: two roundings); the guided lengths of the
+// tour's own edges are a second table in LDS beside the plain ones, which the descent and the left-to-right tour cost keep
+// reading.  Every scan is a handful of wavefront-sized pieces -- n candidates of 2-opt, at most six chains of n landing edges
+// each -- spread over the workgroup and closed by the same arg-min as the all-to-all scans.
+struct PlainD {
+    const double *c;
+    int n;
+    __device__ __forceinline__ double operator()(int x, int y) const { return c[x * n + y]; }
+};
+struct GuidedD {
+    const double *c;
+    const int32_t *pen;
+    double k;
+    int n;
+    __device__ __forceinline__ double operator()(int x, int y) const {
+        const int q = x * n + y;
+        const double kp = k * (double)pen[q];            // algorithms.py:164: k * penalty, rounded, then added
+        return c[q] + kp;
+    }
+};
+
+// Ctl | edge lengths [n] | tour | tour | tour (the best one) | guided edge lengths [n] | arg-max slots: 16 x (fp64, int32)
+__host__ __device__ inline size_t guided_lds(int n) {
+    return ils_lds(n) + oropt_r16((size_t)n * sizeof(double)) + oropt_r16(kOrOptWaves * sizeof(double)) +
+           oropt_r16(kOrOptWaves * sizeof(int32_t));
+}
+
+// two_opt_o2a (operators.py:53-73) at position i, threads over j; eg[p] = the (guided) length of the tour edge at position p
+template <class DG>
+__device__ __forceinline__ void scan_two_opt_o2a(const int32_t *t, const double *eg, const DG &dg, int n, int i, int tid, int nthr,
+                                                 double &bd, int &bk) {
+    for (int j = 1 + tid; j <= n - 1; j += nthr) {
+        if (j - i < 2 && i - j < 2) continue;
+        const int lo = i < j ? i : j, hi = i < j ? j : i;
+        double delta = dg(t[lo], t[hi]) + dg(t[lo - 1], t[hi - 1]);      // operators.py:25-28, left to right
+        delta = delta - eg[lo - 1];
+        delta = delta - eg[hi - 1];
+        consider<false>(delta, j, bd, bk);
+    }
+}
+
+// the Or-opt candidates (s, L, rev, j) whose chain t[s .. s+L-1] holds position i, in the key order of the all-to-all scan.  A
+// piece of work is one chain and 64 landing edges p; pieces go round the wavefronts.  Only the chain's own edges are skipped
+// (j == s): the rev == 0, j == s - 1 candidate stays, as relocate_o2a (operators.py:106-126) has it
+template <class DG>
+__device__ __forceinline__ void scan_or_opt_o2a(const int32_t *t, const double *eg, const DG &dg, int n, int i, int max_seg, int reverse,
+                                                int wave, int nwaves, int lane, double &bd, int &bk) {
+    const int nblk = (n + kWave - 1) / kWave;
+    int piece = 0;
+    for (int s = i - max_seg + 1 > 1 ? i - max_seg + 1 : 1; s <= i; ++s) {
+        for (int L = i - s + 1; L <= max_seg && s + L - 1 <= n - 1; ++L) {
+            for (int blk = 0; blk < nblk; ++blk, ++piece) {
+                if (piece % nwaves != wave) continue;
+                const int p = blk * kWave + lane;
+                if (p >= n || (p >= s - 1 && p <= s + L - 1)) continue;
+                const int s1 = t[s], sL = t[s + L - 1];
+                const double pre = (-eg[s - 1] - eg[s + L - 1]) + dg(t[s - 1], t[s + L]);
+                const int j = p <= s - 2 ? p + 1 : p + 1 - L;
+                const int tp = t[p], tq = t[p + 1];
+                const double head = pre - eg[p];
+                consider<false>((head + dg(s1, tp)) + dg(sL, tq), or_opt_key(s, L, 0, j), bd, bk);
+                if (reverse && L >= 2) consider<false>((head + dg(sL, tp)) + dg(s1, tq), or_opt_key(s, L, 1, j), bd, bk);
+            }
+        }
+    }
+}
+
+// the first greatest (value, position) of the workgroup (algorithms.py:153-159: `util > max_util or max_util_e is None`);
+// pos == kNoKey: a thread without a candidate.  sv / sp: one slot per wavefront, reused only behind a barrier of the caller's
+__device__ __forceinline__ void block_argmax_first(double *sv, int32_t *sp, int wave, int nwaves, int lane, double &v, int &pos) {
+    wave_argmax_first(v, pos);
+    if (nwaves == 1) return;
+    if (lane == 0) { sv[wave] = v; sp[wave] = pos; }
+    __syncthreads();
+    v = sv[0]; pos = sp[0];
+    for (int w = 1; w < nwaves; ++w) {
+        const double ov = sv[w]; const int op = sp[w];
+        if (op != kNoKey && (pos == kNoKey || ov > v || (ov == v && op < pos))) { v = ov; pos = op; }
+    }
+}
+
+__global__ __launch_bounds__(kWave *kOrOptWaves) void or_opt_o2a_kernel(const int32_t *tour, const double *D, const int32_t *pos, int n,
+                                                                        int max_seg, int reverse, double *delta, int32_t *move,
+                                                                        int32_t *new_tour) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const Carve k = carve(smem, n);
+    const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+    const int lane = tid & (kWave - 1), wave = tid / kWave, nwaves = nthr / kWave;
+    const double *c = D + (size_t)b * n * n;
+    const int32_t *tin = tour + (size_t)b * (n + 1);
+    int32_t *tout = new_tour + (size_t)b * (n + 1);
+    const int i = pos[b];
+
+    for (int q = tid; q <= n; q += nthr) k.ta[q] = tin[q];
+    const int bad = asymmetric(c, n, tid, nthr);         // (its barrier also publishes the tour)
+    double bd = 0.0;
+    int bk = kNoKey;
+    if (!bad && i >= 1 && i <= n - 1) {                  // a position outside 1..n-1 has no candidates
+        edge_lengths(k.ta, c, n, k.e, tid, nthr);
+        __syncthreads();
+        int phase = 0;
+        scan_or_opt_o2a(k.ta, k.e, PlainD{c, n}, n, i, max_seg, reverse, wave, nwaves, lane, bd, bk);
+        block_reduce_best<false>(k.ctl, phase, wave, nwaves, lane, bd, bk);
+    }
+    const bool none = bk == kNoKey;
+    const int s = bk >> 13, L = ((bk >> 11) & 3) + 1, rev = (bk >> 10) & 1, j = bk & 1023;
+    for (int q = tid; q <= n; q += nthr) tout[q] = k.ta[none ? q : or_opt_src(q, s, L, rev, j)];
+    if (tid == 0) {
+        delta[b] = bad ? NAN : bd;
+        int32_t *m = move + (size_t)b * 4;
+        m[0] = none ? -1 : s; m[1] = none ? -1 : L; m[2] = none ? -1 : rev; m[3] = none ? -1 : j;
+    }
+}
+
+// guided local search: descent, then `outer_iters` times { penalty steps until perturbation_moves moves are applied, descent,
+// keep the better tour }.  Every thread holds the same cost, counters, status and penalised edge (kernel arguments, values out
+// of a workgroup reduction, LDS behind a barrier), so every branch around a barrier is uniform.
+__global__ __launch_bounds__(kWave *kOrOptWaves) void guided_or_opt_kernel(
+    const int32_t *tour, const double *cost_in, const double *D, const double *guides, int G, int B, const double *k_in, int32_t *penalty,
+    int n, int outer_iters, int iter0, int perturbation_moves, int max_seg, int reverse, int max_moves, int max_steps, int32_t *tour_out,
+    double *cost_out, int32_t *best_tour, double *best_cost_out, int32_t *moves_out, int32_t *steps_out, int32_t *status_out,
+    double *trace_cost, int trace_cap, int32_t *trace_len) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const Carve k = carve(smem, n);
+    double *eg = reinterpret_cast<double *>(smem + ils_lds(n));
+    double *sv = eg + oropt_r16((size_t)n * sizeof(double)) / sizeof(double);
+    int32_t *sp = reinterpret_cast<int32_t *>(sv + oropt_r16(kOrOptWaves * sizeof(double)) / sizeof(double));
+    const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+    const int lane = tid & (kWave - 1), wave = tid / kWave, nwaves = nthr / kWave;
+    const double *c = D + (size_t)b * n * n;
+    int32_t *pen = penalty + (size_t)b * n * n;
+    const int32_t *tin = tour + (size_t)b * (n + 1);
+    double *trace = trace_cost ? trace_cost + (size_t)b * trace_cap : nullptr;
+    const double kk = k_in[b];
+    const GuidedD dg{c, pen, kk, n};
+
+    int32_t *cur = k.ta, *nxt = k.tb, *best = k.tc;
+    for (int q = tid; q <= n; q += nthr) cur[q] = best[q] = tin[q];
+    double cost = cost_in[b], best_cost = cost;
+    int moves = 0, steps = 0, status = 0;
+    if (asymmetric(c, n, tid, nthr)) {                   // (its barrier also publishes the tour)
+        status = kOrOptStatusAsymmetric;                 // not searched: the outputs are the inputs
+    } else {
+        edge_lengths(cur, c, n, k.e, tid, nthr);
+        __syncthreads();
+        int phase = 0;
+        descend(cur, nxt, k.e, k.ctl, phase, c, n, max_seg, reverse, max_moves, tid, nthr, lane, wave, nwaves, cost, moves, status, trace,
+                trace_cap);                              // algorithms.py:142
+        for (int q = tid; q <= n; q += nthr) best[q] = cur[q];           // :143
+        best_cost = cost;
+        for (int it = 0; it < outer_iters && status == 0; ++it) {
+            const double *guide = guides + ((size_t)((iter0 + it) % G) * B + b) * n * n;       // :147
+            int moves_it = 0;
+            while (moves_it < perturbation_moves && status == 0) {       // :151
+                if (steps >= max_steps) { status = kGuidedStatusStepCap; break; }
+                ++steps;
+                double uv = 0.0;                         // :153-159, the first greatest utility
+                int me = kNoKey;
+                for (int p = tid; p < n; p += nthr) {
+                    const int q = cur[p] * n + cur[p + 1];
+                    const double u = guide[q] / (1.0 + (double)pen[q]);
+                    if (me == kNoKey || u > uv) { uv = u; me = p; }
+                }
+                block_argmax_first(sv, sp, wave, nwaves, lane, uv, me);
+                if (me < 0 || me >= n) me = 0;           // (utilities that are all NaN)
+                const int na = cur[me], nb = cur[me + 1];
+                if (tid == 0) {                          // :161; one thread, plain stores
+                    pen[na * n + nb] += 1;
+                    pen[nb * n + na] += 1;
+                }
+                __syncthreads();                         // the counters are visible to the workgroup from here
+                for (int p = tid; p < n; p += nthr) eg[p] = k.e[p] + kk * (double)pen[cur[p] * n + cur[p + 1]];
+                for (int s = 0; s < 2 && status == 0; ++s) {             // :167
+                    const int node = s ? nb : na;
+                    if (node == cur[0]) continue;        // :168
+                    if (tid == 0) k.ctl->flag = 0;       // :169 cur_tour.index(node): the thread that holds it says where
+                    __syncthreads();                     // (this barrier also publishes eg)
+                    for (int q = 1 + tid; q < n; q += nthr)
+                        if (cur[q] == node) k.ctl->flag = q;
+                    __syncthreads();
+                    const int i = k.ctl->flag;
+                    if (i < 1 || i > n - 1) continue;    // (a tour that is no permutation)
+                    for (int op = 0; op < 2 && status == 0; ++op) {      // :171
+                        double bd = 0.0;
+                        int bk = kNoKey;
+                        if (op == 0) scan_two_opt_o2a(cur, eg, dg, n, i, tid, nthr, bd, bk);
+                        else scan_or_opt_o2a(cur, eg, dg, n, i, max_seg, reverse, wave, nwaves, lane, bd, bk);
+                        block_reduce_best<false>(k.ctl, phase, wave, nwaves, lane, bd, bk);
+                        if (bk == kNoKey) continue;
+                        if (op == 0) {
+                            const int lo = i < bk ? i : bk, hi = i < bk ? bk : i;
+                            for (int q = tid; q <= n; q += nthr) nxt[q] = cur[two_opt_src(q, lo, hi)];
+                        } else {
+                            const int s0 = bk >> 13, L = ((bk >> 11) & 3) + 1, rev = (bk >> 10) & 1, j = bk & 1023;
+                            for (int q = tid; q <= n; q += nthr) nxt[q] = cur[or_opt_src(q, s0, L, rev, j)];
+                        }
+                        __syncthreads();                 // the scan's reads of cur / eg are over, the new tour is complete
+                        int32_t *x = cur; cur = nxt; nxt = x;
+                        for (int p = tid; p < n; p += nthr) {
+                            const int q = cur[p] * n + cur[p + 1];
+                            const double d = c[q];
+                            k.e[p] = d;
+                            eg[p] = d + kk * (double)pen[q];
+                        }
+                        __syncthreads();
+                        if (tid == 0) {                  // :176 tour_cost on the real weights, left to right from 0
+                            double sum = 0.0;
+                            for (int p = 0; p < n; ++p) sum = sum + k.e[p];
+                            k.ctl->cost = sum;
+                        }
+                        __syncthreads();
+                        cost = k.ctl->cost;
+                        if (tid == 0 && trace && moves < trace_cap) trace[moves] = cost;
+                        ++moves;
+                        ++moves_it;                      // :185
+                        if (moves >= max_moves) status = kOrOptStatusMoveCap;
+                    }
+                }
+                __syncthreads();                         // the last scans and searches of this step are over
+            }
+            if (status == 0)                             // :188
+                descend(cur, nxt, k.e, k.ctl, phase, c, n, max_seg, reverse, max_moves, tid, nthr, lane, wave, nwaves, cost, moves, status,
+                        trace, trace_cap);
+            if (cost < best_cost) {                      // :190-191, also for a run a cap has ended
+                for (int q = tid; q <= n; q += nthr) best[q] = cur[q];
+                best_cost = cost;
+            }
+        }
+    }
+    __syncthreads();
+    int32_t *tout = tour_out + (size_t)b * (n + 1), *bout = best_tour + (size_t)b * (n + 1);
+    for (int q = tid; q <= n; q += nthr) { tout[q] = cur[q]; bout[q] = best[q]; }
+    if (tid == 0) {
+        cost_out[b] = cost; best_cost_out[b] = best_cost; moves_out[b] = moves; steps_out[b] = steps; status_out[b] = status;
+        if (trace_len) trace_len[b] = moves < trace_cap ? moves : trace_cap;
+    }
+}
+
 }  // namespace
 
 int or_opt_threads(int n) {
@@ -380,6 +622,28 @@ hipError_t launch_ils(const int32_t *tour, const double *cost, const double *D, 
     (void)hipGetLastError();
     hipLaunchKernelGGL(ils_kernel, dim3(B), dim3(or_opt_threads(n)), ils_lds(n), stream, tour, cost, D, n, kicks, kick0, max_seg,
                        reverse ? 1 : 0, max_moves, seed, u, tour_out, cost_out, moves, accepted, status, trace_cost);
+    return hipGetLastError();
+}
+
+hipError_t launch_or_opt_o2a(const int32_t *tour, const double *D, const int32_t *pos, int B, int n, int max_seg, int reverse,
+                             double *delta, int32_t *move, int32_t *new_tour, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(or_opt_o2a_kernel, dim3(B), dim3(or_opt_threads(n)), oropt_lds(n), stream, tour, D, pos, n, max_seg, reverse ? 1 : 0,
+                       delta, move, new_tour);
+    return hipGetLastError();
+}
+
+int guided_or_opt_lds_bytes(int n) { return (int)guided_lds(n); }
+
+hipError_t launch_guided_or_opt(const int32_t *tour, const double *cost, const double *D, const double *guides, int G, const double *k,
+                                int32_t *penalty, int B, int n, int outer_iters, int iter0, int perturbation_moves, int max_seg,
+                                int reverse, int max_moves, int max_steps, int32_t *tour_out, double *cost_out, int32_t *best_tour,
+                                double *best_cost, int32_t *moves, int32_t *steps, int32_t *status, double *trace_cost, int trace_cap,
+                                int32_t *trace_len, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(guided_or_opt_kernel, dim3(B), dim3(or_opt_threads(n)), guided_lds(n), stream, tour, cost, D, guides, G, B, k,
+                       penalty, n, outer_iters, iter0, perturbation_moves, max_seg, reverse ? 1 : 0, max_moves, max_steps, tour_out,
+                       cost_out, best_tour, best_cost, moves, steps, status, trace_cost, trace_cap, trace_len);
     return hipGetLastError();
 }
 

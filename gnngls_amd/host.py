@@ -401,6 +401,163 @@ def ils(tour, cost, D, kicks, max_seg=3, reverse=True, max_moves=None, u=None, s
     return cur, cur_cost, moves, accepted, ILS_STATUS_MOVE_CAP if capped else 0, trace
 
 
+def two_opt_o2a(tour, D, i):
+    """The reference's two_opt_o2a, best improvement (operators.py:53-73): position i against every j in 1..n-1 with
+    abs(i - j) >= 2, two_opt_cost operand by operand, the rule `delta < best_delta and not np.isclose(0, delta)` -- the first j with
+    the smallest qualifying delta.  -> (delta, (i, j)) or (0, None)."""
+    import numpy as np
+    t = np.asarray(tour)
+    n = len(t) - 1
+    assert 1 <= i <= n - 1
+    D = np.asarray(D, dtype=np.float64)
+    j = np.arange(1, n)
+    lo, hi = np.minimum(i, j), np.maximum(i, j)
+    a, b, c, d = t[lo], t[lo - 1], t[hi], t[hi - 1]
+    delta = D[a, c] + D[b, d] - D[a, b] - D[c, d]
+    ok = (np.abs(i - j) >= 2) & (delta < 0) & ~_isclose0(delta)
+    if not ok.any():
+        return 0, None
+    m = delta[ok].min()
+    return m, (i, int(j[ok & (delta == m)][0]))
+
+
+def or_opt_o2a(tour, D, i, max_seg=3, reverse=True):
+    """One best-improvement scan of the Or-opt candidates (s, L, rev, j) whose chain t[s .. s+L-1] contains position i:
+    1 <= s <= i <= s+L-1 <= n-1, 1 <= L <= max_seg, in ascending (s, L, rev, j), with or_opt_cost's delta and or_opt_a2a's rule.
+    Only j == s is skipped, in both orientations: the `rev == 0, j == s-1` skip of the all-to-all scan does not apply (the
+    reference's relocate_o2a, operators.py:106-126, evaluates it, and its twin move is not in this set).  -> (delta,
+    (s, L, rev, j)) or (0, None).  With max_seg=1, reverse=False it is relocate_o2a operand by operand."""
+    import numpy as np
+    assert 1 <= max_seg <= 3
+    t = np.asarray(tour)
+    n = len(t) - 1
+    assert 1 <= i <= n - 1
+    D = np.asarray(D, dtype=np.float64)
+    best = None                                           # (delta, s, L, rev, j): ascending s, L, rev, j below, strict <
+    for s in range(max(1, i - max_seg + 1), i + 1):
+        for L in range(i - s + 1, max_seg + 1):
+            if s + L - 1 > n - 1:
+                break
+            j = np.arange(1, n - L + 1)
+            a, s1, sL, c = t[s - 1], t[s], t[s + L - 1], t[s + L]
+            d = t[np.where(j - 1 < s, j - 1, j - 1 + L)]
+            e = t[np.where(j < s, j, j + L)]
+            pre = -D[a, s1] - D[sL, c] + D[a, c] - D[d, e]
+            for rev in ((0, 1) if (reverse and L >= 2) else (0,)):
+                delta = (pre + D[d, sL] + D[s1, e]) if rev else (pre + D[d, s1] + D[sL, e])
+                ok = (j != s) & (delta < 0) & ~_isclose0(delta)
+                if not ok.any():
+                    continue
+                m = delta[ok].min()
+                if best is None or m < best[0]:
+                    best = (m, s, L, rev, int(j[ok & (delta == m)][0]))
+    if best is None:
+        return 0, None
+    return best[0], best[1:]
+
+
+GUIDED_STATUS_MOVE_CAP = 6                                # GNNGLS_STATUS_MOVE_CAP
+GUIDED_STATUS_STEP_CAP = 7                                # GNNGLS_STATUS_STEP_CAP
+
+
+def guided_or_opt(tour, cost, D, guides, outer_iters, k, penalty, perturbation_moves=20, max_seg=3, reverse=True, max_moves=None,
+                  max_steps=None, iter0=0, log=None):
+    """Guided local search over 2-opt and Or-opt of one instance in NumPy, the definition of include/gnngls_hip.h restated -- what
+    gnngls_amd.ops.guided_or_opt is compared against bit for bit.  It is the reference's guided_local_search
+    (algorithms.py:135-195) with relocate_a2a / relocate_o2a replaced by or_opt_a2a / or_opt_o2a(max_seg, reverse), `outer_iters`
+    iterations in the deadline's place, k an input (the reference's 0.1 * init_cost / n) and penalty an int32 [n,n] symmetric
+    matrix updated IN PLACE.
+      1. cur, cur_cost = or_opt_descent(tour, cost); best = cur.
+      2. for it = 0 .. outer_iters-1: guide = guides[(iter0 + it) % G]; moves_it = 0; while moves_it < perturbation_moves:
+           the penalised edge (a, b) = the first tour edge of the greatest guide[a,b] / (1 + penalty[a,b]) (lines 153-159);
+           penalty[a,b] += 1, penalty[b,a] += 1; Dg = D + k * penalty, elementwise, two roundings;
+           for each of a, b (in tour order) that is not the depot cur[0]: i = cur.index(node), taken once; two_opt_o2a(cur, Dg, i),
+           then or_opt_o2a(cur, Dg, i) on the tour the first left; a found move replaces cur, cur_cost = the tour's cost under D
+           summed left to right from 0, moves_it += 1.
+         then cur, cur_cost = or_opt_descent(cur, cur_cost) on D, and best = cur on cur_cost < best_cost.
+      3. max_moves (None: no cap) counts the applied moves of every kind and is checked after each; max_steps (None: no cap)
+         counts penalisations and is checked before each.  A cap ends the run where it stands, the `cur_cost < best_cost`
+         bookkeeping is applied to what the run holds, the status is GUIDED_STATUS_MOVE_CAP / GUIDED_STATUS_STEP_CAP.
+    A run of K1 iterations, then one of K2 with iter0 = K1 from the first run's CURRENT tour, cost and penalties under the same k
+    is the run of K1 + K2 iterations; the caller keeps the better of the two bests under <, ties to the earlier.
+    -> (cur, cur_cost, best, best_cost, moves, steps, status, trace): trace = the cost after every applied move.  log (a list):
+    gets one (it, op, move) per move of the penalty steps, op 0 = 2-opt (i, j), 1 = Or-opt (s, L, rev, j)."""
+    import numpy as np
+    n = len(tour) - 1
+    assert n >= 4 and outer_iters >= 0 and iter0 >= 0 and perturbation_moves >= 0
+    D = np.asarray(D, dtype=np.float64)
+    if outer_iters > 0:
+        guides = np.asarray(guides, dtype=np.float64)
+        guides = guides[None] if guides.ndim == 2 else guides
+    assert penalty.dtype == np.int32 and penalty.shape == (n, n)
+    k = np.float64(k)
+
+    def left(moves):
+        return None if max_moves is None else max_moves - moves
+
+    cur, cur_cost, moves, trace = or_opt_descent(tour, cost, D, max_seg, reverse, left(0))
+    trace = list(trace)
+    best, best_cost = cur, cur_cost
+    steps = 0
+    status = GUIDED_STATUS_MOVE_CAP if max_moves is not None and moves >= max_moves else 0
+    for it in range(outer_iters):
+        if status:
+            break
+        guide = guides[(iter0 + it) % len(guides)]
+        moves_it = 0
+        while moves_it < perturbation_moves and not status:
+            if max_steps is not None and steps >= max_steps:
+                status = GUIDED_STATUS_STEP_CAP
+                break
+            steps += 1
+            t = np.asarray(cur)
+            util = guide[t[:-1], t[1:]] / (1 + penalty[t[:-1], t[1:]])
+            me = 0
+            for p in range(1, n):                         # `util > max_util or max_util_e is None`: the first greatest
+                if util[p] > util[me]:
+                    me = p
+            a, b = cur[me], cur[me + 1]
+            penalty[a, b] += 1
+            penalty[b, a] += 1
+            Dg = D + k * penalty
+            for node in (a, b):
+                if status or node == cur[0]:
+                    continue
+                i = cur.index(node)
+                for op in (0, 1):
+                    if op == 0:
+                        delta, move = two_opt_o2a(cur, Dg, i)
+                    else:
+                        delta, move = or_opt_o2a(cur, Dg, i, max_seg, reverse)
+                    if move is None:
+                        continue
+                    if op == 0:
+                        lo, hi = min(move), max(move)
+                        cur = cur[:lo] + cur[hi - 1:lo - 1:-1] + cur[hi:]      # operators.py:11
+                    else:
+                        cur = or_opt(cur, *move)
+                    cur_cost = 0.0
+                    for x, y in zip(cur[:-1], cur[1:]):
+                        cur_cost = cur_cost + D[x, y]
+                    trace.append(cur_cost)
+                    if log is not None:
+                        log.append((it, op, move))
+                    moves += 1
+                    moves_it += 1
+                    if max_moves is not None and moves >= max_moves:
+                        status = GUIDED_STATUS_MOVE_CAP
+                        break
+        if not status:
+            cur, cur_cost, m, tr = or_opt_descent(cur, cur_cost, D, max_seg, reverse, left(moves))
+            moves += m
+            trace += list(tr)
+            if max_moves is not None and moves >= max_moves:
+                status = GUIDED_STATUS_MOVE_CAP
+        if cur_cost < best_cost:
+            best, best_cost = cur, cur_cost
+    return cur, cur_cost, best, best_cost, moves, steps, status, trace
+
+
 def fixed_edge_tour(G, e, scale=None, lkh_path=None, base_tour=None, label_iters=None, perturbation_moves=None, **kwargs):
     """A tour of G that holds edge e (reference __init__.py:63-79: LKH with e fixed).  Here: the fixed-edge search of
     gnngls_amd.labels on the device -- guided_local_search on G's weights with e's weight lowered by M, guide = those weights,

@@ -519,6 +519,107 @@ def ils(tour, cost, D, kicks, max_seg=3, reverse=True, max_moves=None, seed=0, u
     return r
 
 
+STATUS_STEP_CAP = 7                                           # GNNGLS_STATUS_STEP_CAP
+_INT32_MAX = 2 ** 31 - 1
+
+
+def or_opt_o2a(tour, D, pos, max_seg=3, reverse=True):
+    """One best-improvement scan, for every tour of a batch in one launch, of the Or-opt candidates (s, L, rev, j) whose chain
+    t[s .. s+L-1] contains the position pos[b] -- the segment-move form of the reference's relocate_o2a (operators.py:106-126),
+    which it is with max_seg=1, reverse=False (include/gnngls_hip.h states the candidates and the order; host.or_opt_o2a restates
+    them in NumPy, bit for bit).  tour [B,n+1] int32, D [B,n,n] fp64 bitwise symmetric, pos [B] int32 in 1..n-1 -> (delta [B]
+    fp64, 0.0 when nothing qualifies; move [B,4] int32 = s, L, rev, j, -1s when none; new_tour [B,n+1] int32).  A matrix that is
+    not symmetric raises."""
+    B, n = _check_shapes(tour, D)
+    assert pos.dtype == torch.int32 and pos.shape == (B,), f"pos shape {tuple(pos.shape)} is not [{B}]"
+    if bool(((pos < 1) | (pos > n - 1)).any()):
+        raise ValueError(f"or_opt_o2a: positions must be in 1..{n - 1}")
+    delta = torch.empty((B,), dtype=torch.float64, device=tour.device)
+    move = torch.empty((B, 4), dtype=torch.int32, device=tour.device)
+    new_tour = torch.empty_like(tour)
+    f = _or_opt_entry("gnngls_or_opt_o2a")
+    _lib.check(f(_lib.ptr(tour.contiguous()), _lib.ptr(D.contiguous()), _lib.ptr(pos.to(tour.device).contiguous()), B, n, int(max_seg),
+                 int(bool(reverse)), _lib.ptr(delta), _lib.ptr(move), _lib.ptr(new_tour), _lib.current_stream()), "or_opt_o2a")
+    bad = torch.isnan(delta).nonzero().flatten().tolist()
+    if bad:
+        _raise_asymmetric("or_opt_o2a", bad)
+    return delta, move, new_tour
+
+
+@dataclass
+class GuidedOrOptResult:
+    tour: torch.Tensor           # [B,n+1] int32 the current tour: what a following run (iter0) starts from
+    cost: torch.Tensor           # [B] fp64 its cost
+    best_tour: torch.Tensor      # [B,n+1] int32
+    best_cost: torch.Tensor      # [B] fp64
+    moves: torch.Tensor          # [B] int32 applied moves of every kind
+    steps: torch.Tensor          # [B] int32 penalisations
+    status: torch.Tensor         # [B] int32 STATUS_OK, STATUS_MOVE_CAP, STATUS_STEP_CAP or (guided_or_opt_launch only) STATUS_ASYMMETRIC
+    penalty: torch.Tensor        # [B,n,n] int32 the counters after the run (the caller's tensor when one was given)
+    k: torch.Tensor              # [B] fp64 the penalty weight of the run
+    trace_cost: torch.Tensor     # [B,trace_cap] fp64 the cost after each of the first trace_cap moves, or None
+    trace_len: torch.Tensor      # [B] int32 min(moves, trace_cap)
+
+
+def guided_or_opt_launch(tour, cost, D, guides, outer_iters, k=None, penalty=None, perturbation_moves=20, max_seg=3, reverse=True,
+                         max_moves=None, max_steps=None, iter0=0, trace_cap=0):
+    """The launch behind guided_or_opt and torch.ops.gnngls.guided_or_opt: -> GuidedOrOptResult, nothing raised for an instance
+    whose matrix is not symmetric (its status is STATUS_ASYMMETRIC, its outputs are its inputs)."""
+    B, n = _check_shapes(tour, D)
+    dev = tour.device
+    assert cost.dtype == torch.float64 and cost.shape == (B,), f"cost shape {tuple(cost.shape)} is not [{B}]"
+    outer_iters, iter0, perturbation_moves, trace_cap = int(outer_iters), int(iter0), int(perturbation_moves), int(trace_cap)
+    G = 0
+    if guides is not None:
+        assert guides.dtype == torch.float64 and guides.dim() == 4 and guides.shape[1:] == (B, n, n), \
+            f"guides shape {tuple(guides.shape)} is not [G,{B},{n},{n}]"
+        G = guides.shape[0]
+        guides = guides.to(dev).contiguous()
+    if k is None:
+        # algorithms.py:137 as Python evaluates it: on the host (a tensor divided by a scalar is multiplied by its reciprocal)
+        k = as_dev(0.1 * cost.cpu().numpy() / n, torch.float64).to(dev)
+    assert k.dtype == torch.float64 and k.shape == (B,), f"k shape {tuple(k.shape)} is not [{B}]"
+    if penalty is None:
+        penalty = torch.zeros((B, n, n), dtype=torch.int32, device=dev)
+    assert penalty.dtype == torch.int32 and penalty.shape == (B, n, n) and penalty.is_contiguous() and penalty.device == dev, \
+        f"penalty must be a contiguous int32 [{B},{n},{n}] tensor on the tours' device (it is updated in place)"
+    if max_moves is None:
+        max_moves = min(100 * n * (outer_iters + 1), _INT32_MAX)
+    if max_steps is None:
+        max_steps = min(max(100 * max(perturbation_moves, 1) * outer_iters, 1), _INT32_MAX)
+    tour_out, best_tour = torch.empty_like(tour), torch.empty_like(tour)
+    cost_out, best_cost = (torch.empty((B,), dtype=torch.float64, device=dev) for _ in range(2))
+    moves, steps, status, trace_len = (torch.zeros((B,), dtype=torch.int32, device=dev) for _ in range(4))
+    trace = torch.zeros((B, trace_cap), dtype=torch.float64, device=dev) if trace_cap > 0 else None
+    f = _or_opt_entry("gnngls_guided_or_opt_run")
+    _lib.check(f(_lib.ptr(tour.contiguous()), _lib.ptr(cost.contiguous()), _lib.ptr(D.contiguous()), _lib.ptr(guides), G,
+                 _lib.ptr(k.to(dev).contiguous()), _lib.ptr(penalty), B, n, outer_iters, iter0, perturbation_moves, int(max_seg),
+                 int(bool(reverse)), int(max_moves), int(max_steps), _lib.ptr(tour_out), _lib.ptr(cost_out), _lib.ptr(best_tour),
+                 _lib.ptr(best_cost), _lib.ptr(moves), _lib.ptr(steps), _lib.ptr(status), _lib.ptr(trace), trace_cap,
+                 _lib.ptr(trace_len), _lib.current_stream()), "guided_or_opt_run")
+    return GuidedOrOptResult(tour_out, cost_out, best_tour, best_cost, moves, steps, status, penalty, k, trace, trace_len)
+
+
+def guided_or_opt(tour, cost, D, guides, outer_iters, k=None, penalty=None, perturbation_moves=20, max_seg=3, reverse=True,
+                  max_moves=None, max_steps=None, iter0=0, trace_cap=0):
+    """Guided local search over 2-opt and Or-opt of a batch in ONE launch, n <= OR_OPT_MAX_N: the reference's guided_local_search
+    (algorithms.py:135-195) for `outer_iters` iterations with relocate_a2a / relocate_o2a replaced by the Or-opt scans of chains
+    of 1..max_seg nodes (include/gnngls_hip.h states the definition; host.guided_or_opt restates it in NumPy, bit for bit).  With
+    max_seg=1, reverse=False it is gls_run(max_outer_iters=outer_iters) bit for bit.
+    tour [B,n+1] int32, cost [B] fp64, D [B,n,n] fp64 bitwise symmetric, guides [G,B,n,n] fp64 (guides[(iter0 + it) % G] steers
+    iteration it), n >= 4.  k [B] fp64: the penalty weight (None: 0.1 * cost / n in fp64, the reference's); penalty [B,n,n] int32
+    symmetric, updated IN PLACE (None: zeros).  max_moves caps the applied moves (STATUS_MOVE_CAP; None = 100 * n *
+    (outer_iters + 1)), max_steps the penalisations (STATUS_STEP_CAP; None = 100 * perturbation_moves * outer_iters), both
+    clipped to int32.  A run continues an earlier one from its .tour, .cost, .penalty and .k with iter0 = that run's
+    iterations; the caller keeps the better of the two bests.  -> GuidedOrOptResult.  A matrix that is not symmetric raises."""
+    r = guided_or_opt_launch(tour, cost, D, guides, outer_iters, k, penalty, perturbation_moves, max_seg, reverse, max_moves, max_steps,
+                             iter0, trace_cap)
+    bad = (r.status == STATUS_ASYMMETRIC).nonzero().flatten().tolist()
+    if bad:
+        _raise_asymmetric("guided_or_opt", bad)
+    return r
+
+
 def gls_run(D, guides, init_tour, init_cost, perturbation_moves=30, first_improvement=False,
             max_outer_iters=-1, time_limit_s=0.0, watchdog_s=None, trace_cap=0, want_trace_time=False,
             want_penalty=False, penalty_bits=0, retry_overflow=True, imp_cap=0, retry_asymmetric=True):

@@ -1,7 +1,7 @@
 """PyTorch-ROCm custom operators of the hot path: `torch.ops.gnngls.*` (north_star).
 
-Ten operators and, since the Or-opt descent, iterated local search and the 3-opt descent, an eleventh, a twelfth and a thirteenth
-are registered with
+Ten operators and, since the Or-opt descent, iterated local search, the 3-opt descent and guided local search over Or-opt, an
+eleventh to a fourteenth are registered with
 `torch.library` over the C ABI of libgnngls_hip.so (include/gnngls_hip.h).  Each has
 exactly ONE implementation, for the CUDA dispatch key (= HIP on ROCm): there is no CPU kernel behind any of them, so
 calling one with CPU tensors fails in the dispatcher ("no CPU fallback" is structural, not a runtime check).  Shape
@@ -37,6 +37,13 @@ the current HIP stream, take caller-owned contiguous tensors and retain nothing.
     three_opt_descent(tour, cost[B] f64, D, max_moves, trace_capacity) -> (tour, cost, n_moves[B] i32, status[B] i32,
         trace_cost[B,trace_capacity] f64): local_search with the exhaustive 3-opt scan in relocate's place, n <= 256; status 3 as
         for or_opt_descent -- the op reports, gnngls_amd.ops.three_opt_descent raises
+    guided_or_opt(tour, cost[B] f64, D, guides[G,B,n,n] f64, outer_iters, iter0, k[B] f64 or None, penalty[B,n,n] i32 or None,
+        perturbation_moves, max_seg, reverse, max_moves, max_steps, trace_capacity) -> (tour, cost, best_tour, best_cost,
+        n_moves[B] i32, steps[B] i32, status[B] i32, penalty[B,n,n] i32, trace_cost[B,trace_capacity] f64, trace_len[B] i32):
+        guided local search over 2-opt and Or-opt in one launch, n <= 1024 (algorithms.py:135-195 with the Or-opt scans in
+        relocate's places); functional: the given penalties are copied, the counters after the run are returned; max_moves /
+        max_steps <= 0 = the defaults of gnngls_amd.ops.guided_or_opt; status 3 as for or_opt_descent -- the op reports,
+        gnngls_amd.ops.guided_or_opt raises
 """
 import ctypes
 
@@ -61,6 +68,9 @@ _LIB.define("sample_nn_tours(Tensor W, int R, int depot, bool invert, int seed, 
 _LIB.define("ils(Tensor tour, Tensor cost, Tensor D, int kicks, int kick0, int max_seg, bool reverse, int max_moves, int seed, Tensor? u) "
             "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("three_opt_descent(Tensor tour, Tensor cost, Tensor D, int max_moves, int trace_capacity) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
+_LIB.define("guided_or_opt(Tensor tour, Tensor cost, Tensor D, Tensor guides, int outer_iters, int iter0, Tensor? k, Tensor? penalty, "
+            "int perturbation_moves, int max_seg, bool reverse, int max_moves, int max_steps, int trace_capacity) "
+            "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
 
 _workspaces = {}      # device index -> uint8 scratch tensor for the forward (grown on demand, reused across calls)
 
@@ -154,6 +164,18 @@ def _three_opt_descent(tour, cost, D, max_moves, trace_capacity):
 _LIB.impl("three_opt_descent", _three_opt_descent, "CUDA")
 
 
+def _guided_or_opt(tour, cost, D, guides, outer_iters, iter0, k, penalty, perturbation_moves, max_seg, reverse, max_moves, max_steps,
+                   trace_capacity):
+    r = ops.guided_or_opt_launch(tour, cost, D, guides, outer_iters, k, None if penalty is None else penalty.clone().contiguous(),
+                                 perturbation_moves, max_seg, reverse, max_moves if max_moves > 0 else None,
+                                 max_steps if max_steps > 0 else None, iter0, trace_capacity)
+    trace = r.trace_cost if r.trace_cost is not None else torch.zeros((tour.shape[0], 0), dtype=torch.float64, device=tour.device)
+    return r.tour, r.cost, r.best_tour, r.best_cost, r.moves, r.steps, r.status, r.penalty, trace, r.trace_len
+
+
+_LIB.impl("guided_or_opt", _guided_or_opt, "CUDA")
+
+
 # ---- shape functions (fake tensors / tracing); no arithmetic -------------------------------------------------------
 @torch.library.register_fake("gnngls::regret_forward")
 def _(feat, packed_weights, n, heads, head_dim, hidden, layers):
@@ -233,3 +255,12 @@ def _(tour, cost, D, max_moves, trace_capacity):
     i32 = lambda: tour.new_empty((B,), dtype=torch.int32)  # noqa: E731
     return (tour.new_empty(tuple(tour.shape)), cost.new_empty((B,)), i32(), i32(),
             cost.new_empty((B, max(int(trace_capacity), 0)), dtype=torch.float64))
+
+
+@torch.library.register_fake("gnngls::guided_or_opt")
+def _(tour, cost, D, guides, outer_iters, iter0, k, penalty, perturbation_moves, max_seg, reverse, max_moves, max_steps, trace_capacity):
+    B, n = tour.shape[0], D.shape[1]
+    i32 = lambda: tour.new_empty((B,), dtype=torch.int32)  # noqa: E731
+    return (tour.new_empty(tuple(tour.shape)), cost.new_empty((B,)), tour.new_empty(tuple(tour.shape)), cost.new_empty((B,)), i32(), i32(),
+            i32(), tour.new_empty((B, n, n), dtype=torch.int32), cost.new_empty((B, max(int(trace_capacity), 0)), dtype=torch.float64),
+            i32())

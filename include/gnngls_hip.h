@@ -280,6 +280,59 @@ int gnngls_ils_run(const int32_t *tour, const double *cost, const double *D, int
                    int reverse, int max_moves, uint64_t seed, const double *u, int32_t *tour_out, double *cost_out, int32_t *moves,
                    int32_t *accepted, int32_t *status, double *trace_cost, void *stream);
 
+/* ---- guided local search over 2-opt and Or-opt, one launch, n <= GNNGLS_OR_OPT_MAX_N ------------------------------------------
+ * The reference's guided_local_search (algorithms.py:135-195) with relocate_a2a and relocate_o2a replaced by the Or-opt scans --
+ * the KGLS operator set the comment at algorithms.py:147 points to -- built on the descent of gnngls_or_opt_descent, for sizes
+ * the LDS-resident stores of gnngls_gls_run do not reach.  Definition (the contract; gnngls_amd.host.two_opt_o2a, or_opt_o2a and
+ * guided_or_opt restate it in NumPy, bit for bit):
+ *   One-to-all scans at tour position i, 1 <= i <= n-1, on a matrix M:
+ *     two_opt_o2a (operators.py:53-73): j = 1..n-1 with abs(i-j) >= 2; with lo = min(i,j), hi = max(i,j), a = t[lo], b = t[lo-1],
+ *       c = t[hi], d = t[hi-1]:  delta = M[a,c] + M[b,d] - M[a,b] - M[c,d], left to right; the first j of the smallest delta with
+ *       delta < best_delta and not np.isclose(0, delta); the move reverses t[lo .. hi-1].
+ *     or_opt_o2a: the Or-opt candidates (s, L, rev, j) above whose chain t[s .. s+L-1] contains position i -- 1 <= s <= i <=
+ *       s+L-1 <= n-1, 1 <= L <= max_seg -- in ascending (s, L, rev, j), the same delta and rule.  Only j == s is skipped, in both
+ *       orientations: the rev == 0, j == s-1 skip of the all-to-all scan does NOT apply (relocate_o2a, operators.py:106-126,
+ *       evaluates it, and its twin move is not in this set).  With max_seg = 1, reverse = 0 it is relocate_o2a operand by operand.
+ *   gnngls_or_opt_o2a: one or_opt_o2a scan on D at pos[b] for every instance; the outputs are those of gnngls_or_opt_best_move
+ *     (move = s, L, rev, j).  A position outside 1..n-1 has no candidates (delta 0.0, move -1s).
+ *   Run (gnngls_guided_or_opt_run), per instance, with k = k[b], P = penalty[b] (int32 [n,n], symmetric, IN/OUT):
+ *     1. cur, cur_cost = the descent of gnngls_or_opt_descent (max_seg, reverse) from (tour, cost); best = cur.
+ *     2. for it = 0 .. outer_iters-1: guide = guides[(iter0 + it) % G][b]; moves_it = 0; while moves_it < perturbation_moves:
+ *          the penalised edge (a, b) = (t[p], t[p+1]) of the first p with the greatest guide[a,b] / (1 + P[a,b]) (fp64; lines
+ *          153-159: `util > max_util or max_util_e is None`; NaN utilities: which edge is unspecified);
+ *          P[a,b] += 1, P[b,a] += 1;  Dg = D + k * P, elementwise, the product rounded, then the sum (never a fused multiply-add);
+ *          for each of a, b, in this order, that is not the depot t[0]: i = the node's position in cur, taken ONCE (line 169);
+ *          two_opt_o2a(cur, Dg, i), then or_opt_o2a(cur, Dg, i) on the tour the first one left; a found move replaces cur,
+ *          cur_cost = the tour's cost under D summed left to right from 0 (line 176), moves_it += 1, trace_cost gets cur_cost.
+ *        then cur, cur_cost = the descent from (cur, cur_cost) on D, and best = cur iff cur_cost < best_cost (plain <).
+ *     3. max_moves counts the applied moves of every kind and is checked after each; max_steps counts penalisations and is
+ *        checked before each.  A cap ends the run where it stands, the `cur_cost < best_cost` bookkeeping is applied to what the
+ *        run holds, and the status is GNNGLS_STATUS_MOVE_CAP / GNNGLS_STATUS_STEP_CAP.  The run is bounded by outer_iters and
+ *        the two caps only: no wall clock, no watchdog, no spin-wait, nothing shared between workgroups.
+ *   With max_seg = 1 and reverse = 0, k = 0.1 * cost / n and zeroed penalties the best tour, its cost, the trace and the
+ *   penalties are those of guided_local_search run for outer_iters iterations, bit for bit (gnngls_gls_run, max_outer_iters).
+ *   iter0 >= 0 offsets the guide index: a run of K1 iterations followed by a run of K2 with iter0 = K1 from the first run's
+ *   CURRENT tour, cost and penalties under the same k IS a run of K1 + K2 iterations (the second run's first descent applies
+ *   nothing); the caller keeps the better of the two bests under <, ties to the earlier.
+ *   Outputs per instance: tour_out, cost_out the current tour and its cost; best_tour, best_cost; moves [B] all applied moves;
+ *   steps [B] penalisations; status [B] GNNGLS_STATUS_OK, GNNGLS_STATUS_MOVE_CAP, GNNGLS_STATUS_STEP_CAP or
+ *   GNNGLS_STATUS_ASYMMETRIC (D is not bitwise symmetric: not searched, the outputs are the inputs, the penalties untouched);
+ *   trace_cost [B,trace_cap] or NULL: the cost after each of the first trace_cap applied moves (later entries untouched);
+ *   trace_len [B] or NULL: min(moves, trace_cap).
+ * One workgroup per instance, one launch for the batch; the tours live in LDS, D, the guides and the penalties in global memory.
+ * 4 <= n <= GNNGLS_OR_OPT_MAX_N (a larger n returns GNNGLS_ERR_UNSUPPORTED).  Bad arguments -- n < 4 (gnngls_or_opt_o2a: n < 3),
+ * B < 1, outer_iters < 0, iter0 < 0, iter0 + outer_iters > INT32_MAX, outer_iters > 0 with G < 1 or guides NULL,
+ * perturbation_moves < 0, max_seg outside 1..GNNGLS_OR_OPT_MAX_SEG, max_moves < 1, max_steps < 1, trace_cap < 0, a NULL pointer
+ * other than guides / trace_cost / trace_len (GNNGLS_ERR_ARG) -- are rejected on the host before any device work. */
+#define GNNGLS_STATUS_STEP_CAP 7      /* gnngls_guided_or_opt_run: max_steps penalisations were made and the run ended there */
+int gnngls_or_opt_o2a(const int32_t *tour, const double *D, const int32_t *pos, int B, int n, int max_seg, int reverse, double *delta,
+                      int32_t *move, int32_t *new_tour, void *stream);
+int gnngls_guided_or_opt_run(const int32_t *tour, const double *cost, const double *D, const double *guides, int G, const double *k,
+                             int32_t *penalty, int B, int n, int outer_iters, int iter0, int perturbation_moves, int max_seg,
+                             int reverse, int max_moves, int max_steps, int32_t *tour_out, double *cost_out, int32_t *best_tour,
+                             double *best_cost, int32_t *moves, int32_t *steps, int32_t *status, double *trace_cost, int trace_cap,
+                             int32_t *trace_len, void *stream);
+
 /* ---- 3-opt: three tour edges leave and the pieces between them are reconnected in every way that is no 2-opt move -------------
  * The upper end of the classical family beside 2-opt, relocate and Or-opt: every Or-opt candidate above, with any max_seg and
  * reversed or not, is a 3-opt move of the same tour.  The reference has no counterpart.  Definition (the contract;
