@@ -2,7 +2,9 @@
 guided_or_opt_kernel in oropt_kernels.hip) against the NumPy restatement of the definition in gnngls_amd.host (itself pinned in
 tests/test_guided_or_opt_cpu.py, which also asserts that these seeds exercise every kind of move) and, with chains of one node,
 against gls_run: equality always means equal bit patterns of every fp64 value, equal tours and equal penalties.  Instances are
-euclid(default_rng(1000 + n), n) from the nearest-neighbour start, as in the Or-opt tests."""
+euclid(default_rng(1000 + n), n) from the nearest-neighbour start, as in the Or-opt tests; beyond n = 129 (241 to 1024: sixteen
+wavefronts, several landing blocks per chain, the selection key's fields full) one instance per size, the run from the descent's
+local optimum.  Matrices that are no well-scaled distances are in tests/test_search_fuzz_gpu.py."""
 import os
 import sys
 
@@ -154,6 +156,77 @@ def test_beyond_the_lds_resident_stores_it_is_gls_run_on_global_memory():
     o = ops.gls_run(D, g, t, c, perturbation_moves=5, max_outer_iters=1, want_penalty=True, trace_cap=CAP)
     assert torch.equal(r.best_tour, o.best_tour) and same_bits(r.best_cost, o.best_cost) and torch.equal(r.penalty, o.penalty)
     assert torch.equal(r.moves, o.trace_len) and same_bits(r.trace_cost, o.trace_cost) and int(r.steps[0]) >= 2 and not r.status.any()
+
+
+def load_large(n):
+    """One instance of the sizes beyond SIZES: -> (Ds [1,n,n], guides [2,1,n,n], D and the guides on the device, the
+    nearest-neighbour tour on the device, its cost); built once per size."""
+    from gnngls_amd import ops
+    if ("large", n) not in _cache:
+        Ds = gpu_instances(n)[:1]
+        gs = gpu_guides(Ds, n)
+        D = dev(Ds)
+        t = ops.nearest_neighbor(D)
+        _cache["large", n] = (Ds, gs, D, dev(gs), t, ops.tour_cost(t, D))
+    return _cache["large", n]
+
+
+@pytest.mark.parametrize("n", [241, 257, 513, 1000, 1024])
+def test_one_to_all_scan_at_the_large_sizes(n):
+    """From n = 241 every instance runs sixteen wavefronts and the landing blocks of a chain (ceil(n / 64), sixteen at n = 1024) go
+    round them; at n = 1024 the ten-bit fields of the selection key are full.  Positions: the ends, the middle, and every multiple
+    of 64 with its two neighbours (the blocks' edges)."""
+    from gnngls_amd import ops
+    Ds, gs, D, g, t, c = load_large(n)
+    tour = t[0].tolist()
+    pos = {1, 2, 3, n - 3, n - 2, n - 1, (n + 1) // 2} | {m + d for m in range(64, n, 64) for d in (-1, 0, 1)}
+    pos = sorted(p for p in pos if 1 <= p <= n - 1)
+    assert n - 1 in pos and (n < 1024 or 1023 in pos)
+    found = chains = 0
+    for max_seg, reverse in SETTINGS:
+        got = [ops.or_opt_o2a(t, D, dev([p], torch.int32), max_seg, reverse) for p in pos]
+        for p, (delta, move, new) in zip(pos, got):
+            wd, wm = host.or_opt_o2a(tour, Ds[0], p, max_seg, reverse)
+            assert move[0].tolist() == (list(wm) if wm else [-1] * 4), (n, p, max_seg, move[0].tolist(), wm)
+            assert bits(delta.cpu().numpy()[0]) == bits(float(wd)), (n, p, max_seg, float(delta[0]), wd)
+            assert new[0].tolist() == (host.or_opt(tour, *wm) if wm else tour), (n, p, max_seg)
+            found += wm is not None
+            chains += wm is not None and wm[1] >= 2
+    assert found > 0 and chains > 0
+
+
+@pytest.mark.parametrize("n", [241, 300, 513, 1024])
+def test_run_at_the_large_sizes(n):
+    """The run against the host definition beyond n = 129, K = 2 iterations of 5 moves from a local optimum: a full host descent
+    from the nearest-neighbour tour takes hundreds of scans at these sizes, so the start tour is what ops.or_opt_descent leaves
+    (checked against the host on its own in tests/test_or_opt_gpu.py; here it is an input: a closed permutation, its cost summed
+    left to right).  With chains of one node the run is gls_run's, which accepts every one of these sizes (global-memory store).
+    By the host's log the seeds of 513 and 1024 apply 2-opt moves and chains of two or three nodes in their penalty steps."""
+    from gnngls_amd import ops
+    Ds, gs, D, g, t, c = load_large(n)
+    K2, PM2 = 2, 5
+    for max_seg, reverse in [(3, True), (1, False)]:
+        start = ops.or_opt_descent(t, c, D, max_seg, reverse).tour
+        tour = start[0].tolist()
+        assert tour[0] == tour[-1] == 0 and sorted(tour[:-1]) == list(range(n))
+        cost = 0.0
+        for x, y in zip(tour[:-1], tour[1:]):
+            cost = cost + Ds[0][x, y]
+        c0 = dev([cost])
+        r = ops.guided_or_opt(start, c0, D, g, K2, perturbation_moves=PM2, max_seg=max_seg, reverse=reverse, trace_cap=CAP)
+        pen, log = np.zeros((n, n), dtype=np.int32), []
+        w = host.guided_or_opt(tour, cost, Ds[0], gs[:, 0], K2, k_of(cost, n), pen, PM2, max_seg, reverse, log=log)
+        assert w[6] == 0 and len(log) >= K2 * PM2
+        assert_run(r, [(w, pen)], f"n={n} max_seg={max_seg} reverse={reverse}")
+        assert r.status.tolist() == [0]
+        if max_seg == 3:
+            two, longer = sum(op == 0 for _, op, _ in log), sum(op == 1 and m[1] >= 2 for _, op, m in log)
+            assert two >= 1 and longer >= 1, (n, two, longer)
+        else:
+            assert ops.gls_describe_config(n, 1)["store"] == "global"
+            o = ops.gls_run(D, g, start, c0, perturbation_moves=PM2, max_outer_iters=K2, want_penalty=True, trace_cap=CAP)
+            assert torch.equal(r.best_tour, o.best_tour) and same_bits(r.best_cost, o.best_cost) and torch.equal(r.penalty, o.penalty)
+            assert torch.equal(r.moves, o.trace_len) and same_bits(r.trace_cost, o.trace_cost) and not o.status.any()
 
 
 @pytest.mark.parametrize("n", [9, 33, 100])

@@ -242,6 +242,23 @@ def test_largest_instance():
     assert float(r.trace_cost[0, 0]) >= float(r.cost[0])
 
 
+def test_a_large_instance_equals_the_host_definition():
+    """n = 513 against host.ils: sixteen wavefronts, nine landing blocks.  Two kicks from the descent's local optimum (what
+    ops.or_opt_descent leaves: here an input, a closed permutation) -- the first with p1 = 1 and p3 = n - 1, the outermost cuts --
+    under a cap of 20 moves: by the host definition the two repairs take 24 moves (0.8 s on the host), so the cap ends the second."""
+    from gnngls_amd import ops
+    n = 513
+    Ds, D, t, c, tours, costs = load(n, 1)
+    d = ops.or_opt_descent(t, c, D)
+    start = d.tour[0].tolist()
+    assert start[0] == start[-1] == 0 and sorted(start[:-1]) == list(range(n)) and int(d.status[0]) == 0
+    u = np.array([[[0.0, 0.5, U_MAX], [0.37, 0.52, 0.81]]])
+    assert host.double_bridge_cuts(u[0, 0], n) == (1, 257, n - 1)
+    r = ops.ils(d.tour, d.cost, D, 2, 3, True, max_moves=20, u=dev(u), want_trace=True)
+    want = assert_ils(r, [start], d.cost.cpu().numpy(), Ds, 2, 3, True, "n=513 max_moves=20", u=u, max_moves=20)
+    assert want[0][2:5] == (20, 0, host.ILS_STATUS_MOVE_CAP) and len(want[0][5]) == 2     # both kicks ran, the first was repaired
+
+
 def test_mirror_and_torch_operator_return_what_ops_returns():
     from gnngls_amd import algorithms, ops
     import gnngls_amd.torch_ops  # noqa: F401
