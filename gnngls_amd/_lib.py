@@ -44,6 +44,7 @@ SIGNATURES = {
     "gnngls_three_opt_descent": [_vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp],
     "gnngls_three_opt_lds_max_n": [],
     "gnngls_sample_nn_tours": [_vp, _int, _int, _int, _int, _int, _u64, _vp, _vp, _vp, _vp],
+    "gnngls_aco_run": [_vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _i64, _f64, _f64, _int, _int, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "gnngls_gls_run": [_vp, _vp, _int, _int, _int, _vp, _vp, _int, _int, _int, _i64, _f64, _f64,
                        _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp],
     "gnngls_model_packed_floats": [_int, _int],
@@ -127,6 +128,8 @@ _ILS = ("gnngls_ils_run",)
 _THREE_OPT = ("gnngls_three_opt_best_move", "gnngls_three_opt_descent", "gnngls_three_opt_lds_max_n")
 # guided local search over 2-opt and Or-opt (an older build named by GNNGLS_HIP_SO lacks it; ops.or_opt_o2a / guided_or_opt then raise)
 _GUIDED_OR_OPT = ("gnngls_or_opt_o2a", "gnngls_guided_or_opt_run")
+# the ant system (an older build named by GNNGLS_HIP_SO lacks it; ops.aco then raises)
+_ACO = ("gnngls_aco_run",)
 _lib = None
 
 
@@ -149,7 +152,7 @@ def load():
         import torch  # noqa: F401
         L = ctypes.CDLL(SO)
         for name, argtypes in SIGNATURES.items():
-            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS or name in _BOUNDS or name in _SAMPLING or name in _ALPHA or name in _OR_OPT or name in _ILS or name in _THREE_OPT or name in _GUIDED_OR_OPT) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
+            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS or name in _BOUNDS or name in _SAMPLING or name in _ALPHA or name in _OR_OPT or name in _ILS or name in _THREE_OPT or name in _GUIDED_OR_OPT or name in _ACO) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
                 continue              # an older build of the library named by GNNGLS_HIP_SO (same-box A/B of kernel variants)
             f = getattr(L, name)      # AttributeError if the symbol is missing
             f.argtypes = argtypes

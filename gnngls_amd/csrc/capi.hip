@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/gnngls_hip.h"
+#include "aco_kernels.h"
 #include "alpha_kernels.h"
 #include "bounds_kernels.h"
 #include "constructors_kernels.h"
@@ -435,6 +436,38 @@ int gnngls_sample_nn_tours(const double *W, int B, int n, int R, int depot, int 
     if (!W || !tours || !status) return fail(GNNGLS_ERR_ARG, "sample_nn_tours: NULL pointer (W, tours, status)");
     hipError_t e = gnngls::launch_sample_nn_tours(W, B, n, R, depot, invert != 0, seed, u, tours, status, (hipStream_t)stream);
     return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "sample_nn_tours");
+}
+
+static_assert(GNNGLS_ACO_MAX_N == gnngls::kAcoMaxN && GNNGLS_ACO_MAX_ANTS == gnngls::kAcoMaxAnts &&
+              GNNGLS_SAMPLE_BAD_WEIGHTS == gnngls::kAcoStatusBadWeights, "include/gnngls_hip.h and aco_kernels.h disagree");
+
+int gnngls_aco_run(const double *D, const double *H, double *tau, int32_t *best_tour, double *best_cost, int B, int n, int ants, int iters,
+                   int64_t iter0, double rho, double min_ratio, int gb_every, int spread_starts, uint64_t seed, const double *u,
+                   int32_t *iters_done, int32_t *status, double *trace_cost, int32_t *ant_tours, double *ant_cost, void *stream) {
+    if (B < 1) return fail(GNNGLS_ERR_ARG, "aco_run: B=%d must be >= 1", B);
+    if (n < 3) return fail(GNNGLS_ERR_ARG, "aco_run: n=%d must be >= 3", n);
+    if (n > GNNGLS_ACO_MAX_N)
+        return fail(GNNGLS_ERR_UNSUPPORTED, "aco_run: n=%d exceeds the largest supported instance (n <= %d: the state of a walk lives in "
+                    "the registers of one wavefront)", n, GNNGLS_ACO_MAX_N);
+    if (ants < 1) return fail(GNNGLS_ERR_ARG, "aco_run: ants=%d must be >= 1", ants);
+    if (ants > GNNGLS_ACO_MAX_ANTS)
+        return fail(GNNGLS_ERR_UNSUPPORTED, "aco_run: ants=%d exceeds the largest supported colony (ants <= %d)", ants, GNNGLS_ACO_MAX_ANTS);
+    if (iters < 0) return fail(GNNGLS_ERR_ARG, "aco_run: iters=%d must be >= 0", iters);
+    if (iter0 < 0) return fail(GNNGLS_ERR_ARG, "aco_run: iter0=%lld must be >= 0", (long long)iter0);
+    if (iter0 > 0xffffffffLL || (iter0 + iters) * (long long)ants > 0xffffffffLL)
+        return fail(GNNGLS_ERR_ARG, "aco_run: (iter0 + iters) * ants = (%lld + %d) * %d must stay below 2^32 (the walk counter of the "
+                    "generator)", (long long)iter0, iters, ants);
+    if (!(rho > 0.0 && rho < 1.0)) return fail(GNNGLS_ERR_ARG, "aco_run: rho=%g must be in (0, 1)", rho);
+    if (!(min_ratio > 0.0 && min_ratio <= 1.0)) return fail(GNNGLS_ERR_ARG, "aco_run: min_ratio=%g must be in (0, 1]", min_ratio);
+    if (gb_every < 0) return fail(GNNGLS_ERR_ARG, "aco_run: gb_every=%d must be >= 0", gb_every);
+    if (!D || !H || !tau || !best_tour || !best_cost || !iters_done || !status)
+        return fail(GNNGLS_ERR_ARG, "aco_run: NULL pointer (D, H, tau, best_tour, best_cost, iters_done, status)");
+    if ((ant_tours == nullptr) != (ant_cost == nullptr))
+        return fail(GNNGLS_ERR_ARG, "aco_run: NULL pointer (ant_tours and ant_cost are given together or not at all)");
+    hipError_t e = gnngls::launch_aco(D, H, tau, best_tour, best_cost, B, n, ants, iters, (long long)iter0, rho, min_ratio, gb_every,
+                                      spread_starts != 0, seed, u, iters_done, status, trace_cost, ant_tours, ant_cost,
+                                      (hipStream_t)stream);
+    return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "aco_run");
 }
 
 int gnngls_gls_run(const double *D, const double *guides, int n_guides, int B, int n,

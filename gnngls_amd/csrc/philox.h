@@ -1,7 +1,7 @@
 // philox.h -- the counter-based generator of the kernels that draw on the device (sampling_kernels.hip: the sampled walks;
 // oropt_kernels.hip: the cut points of a double-bridge kick).  A draw is a pure function of (seed, counter): it never depends on
 // the launch shape or on a neighbour.  Streams are kept apart by counter word 3: 0 = the walks' (b, r, step, 0), 1 = the kicks'
-// (b, kick, s, 1).  include/gnngls_hip.h states key, counter and the 53-bit formula; tests/test_sampling_cpu.py restates them.
+// (b, kick, s, 1), 2 = the ants' of aco_kernels.hip (b, iteration * ants + ant, step, 2).  include/gnngls_hip.h states key, counter and the 53-bit formula; tests/test_sampling_cpu.py restates them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -558,6 +558,183 @@ def guided_or_opt(tour, cost, D, guides, outer_iters, k, penalty, perturbation_m
     return cur, cur_cost, best, best_cost, moves, steps, status, trace
 
 
+ACO_STATUS_BAD_WEIGHTS = 6                                # GNNGLS_SAMPLE_BAD_WEIGHTS
+ACO_MAX_N, ACO_MAX_ANTS = 1024, 256                       # GNNGLS_ACO_MAX_N, GNNGLS_ACO_MAX_ANTS
+
+
+def _walk_running_sums(p):
+    """The summation order of the sampled walks (include/gnngls_hip.h): p [n] fp64 with +0.0 where the node is no candidate ->
+    (running sum of every node [n], total).  Node j sits on lane j % 64, slot j / 64; per slot an inclusive doubling scan over
+    the 64 lanes (rounds d = 1, 2, .., 32: lane l >= d adds what lane l - d held before the round), the slots chained by
+    base_0 = +0.0, base_{s+1} = base_s + scan_s[63]; total = the last base."""
+    import numpy as np
+    n = len(p)
+    slots = (n + 63) // 64
+    v = np.zeros(slots * 64, dtype=np.float64)
+    v[:n] = p
+    v = v.reshape(slots, 64)
+    for d in (1, 2, 4, 8, 16, 32):
+        old = v.copy()
+        v[:, d:] = old[:, d:] + old[:, :-d]
+    run = np.empty_like(v)
+    base = np.float64(0.0)
+    for s in range(slots):
+        run[s] = base + v[s]
+        base = base + v[s, 63]
+    return run.reshape(-1)[:n], base
+
+
+def sampled_walk(W, start, u):
+    """The sampled walk of gnngls_sample_nn_tours with invert = 0, in NumPy: W [n,n] fp64 weights (W[i,j] with i the current
+    node), u [n-1] uniforms -> the closed tour from `start` (a list of n+1 nodes), or None for a walk that meets weights
+    np.random.choice refuses.  At every step the candidates are the unvisited nodes in ascending id with p_j = W[i,j]; if any
+    p_j is infinite, p_j = 1.0 there and 0.0 elsewhere; if the sum of p is 0, every p_j = 1.0; a NaN, negative or infinite p_j or
+    a total that is not finite and positive ends the walk; x = u * total and the pick is the first candidate with p_j > 0 whose
+    running sum (_walk_running_sums) exceeds x, or the last candidate with p_j > 0 where rounding leaves none."""
+    import numpy as np
+    n = W.shape[0]
+    cand = np.ones(n, dtype=bool)
+    cand[start] = False
+    tour, cur = [int(start)], int(start)
+    with np.errstate(all="ignore"):
+        for s in range(n - 1):
+            p = np.where(cand, W[cur], 0.0)
+            is_inf = np.isinf(p)
+            if is_inf.any():
+                p = np.where(is_inf, 1.0, 0.0)
+            # no candidate negative or NaN: the sum in any order is 0 iff every candidate is a zero
+            zero = not (p > 0).any() if (p >= 0).all() else _walk_running_sums(p)[1] == 0
+            if zero:
+                p = np.where(cand, 1.0, 0.0)
+            if not (p >= 0).all() or np.isinf(p).any():
+                return None
+            run, total = _walk_running_sums(p)
+            if not total > 0 or np.isinf(total):
+                return None
+            x = np.float64(u[s]) * total
+            live = cand & (p > 0)
+            over = np.flatnonzero(live & (run > x))
+            cur = int(over[0]) if len(over) else int(np.flatnonzero(live)[-1])
+            cand[cur] = False
+            tour.append(cur)
+    return tour + [int(start)]
+
+
+def aco_heuristic(G, beta=2.0, kind="inverse"):
+    """The heuristic matrix H of aco from an edge score G [n,n] or [B,n,n] where SMALLER is better (a distance, a regret, alpha),
+    in NumPy; gnngls_amd.ops.aco_heuristic is the same on the device.  kind 'inverse': G ** -beta, the classical 1 / d.  kind
+    'shifted', for scores that reach 0 or below: ((G - min) / (mean - min) + 0.1) ** -beta with min and mean over the
+    off-diagonal entries of each instance (a constant score has mean == min: H is 0 / 0 = NaN, which aco refuses).  The diagonal
+    is 0.  (pow is not pinned bit for bit: H is an INPUT of aco's contract.)"""
+    import numpy as np
+    G = np.asarray(G, dtype=np.float64)
+    n = G.shape[-1]
+    off = ~np.eye(n, dtype=bool)
+    with np.errstate(all="ignore"):
+        if kind == "inverse":
+            H = G ** -float(beta)
+        elif kind == "shifted":
+            lo = np.where(off, G, np.inf).min(axis=(-2, -1), keepdims=True)
+            mean = np.where(off, G, 0.0).sum(axis=(-2, -1), keepdims=True) / (n * (n - 1))
+            H = ((G - lo) / (mean - lo) + 0.1) ** -float(beta)
+        else:
+            raise ValueError(f"aco_heuristic: unknown kind {kind!r} ('inverse' or 'shifted')")
+    return np.where(off, H, 0.0)
+
+
+def aco_init_tau(D, rho):
+    """The start pheromone of aco, [n,n]: every entry 1 / (rho * the cost of the nearest-neighbour tour from node 0) -- the
+    tau_max of a best tour of that cost (ties of the nearest neighbour to the lowest id, the cost summed in tour order)."""
+    import numpy as np
+    D = np.asarray(D, dtype=np.float64)
+    n = D.shape[0]
+    seen = np.zeros(n, dtype=bool)
+    seen[0] = True
+    tour = [0]
+    for _ in range(n - 1):
+        tour.append(int(np.argmin(np.where(seen, np.inf, D[tour[-1]]))))
+        seen[tour[-1]] = True
+    cost = np.float64(0.0)
+    for x, y in zip(tour, tour[1:] + [0]):
+        cost = cost + D[x, y]
+    return np.full((n, n), np.float64(1.0) / (np.float64(rho) * cost))
+
+
+def aco(D, H, ants=16, iters=100, rho=0.1, min_ratio=None, gb_every=0, spread_starts=True, seed=0, u=None, iter0=0, tau=None,
+        best_tour=None, best_cost=None, b=0):
+    """A MAX-MIN ant system of one instance in NumPy, the definition of include/gnngls_hip.h (gnngls_aco_run) restated -- what
+    gnngls_amd.ops.aco is compared against bit for bit.  D, H [n,n] fp64; tau [n,n] (None: aco_init_tau(D, rho)), best_tour
+    [n+1], best_cost (None: no tour yet, +inf).  For t = 0 .. iters-1, g = iter0 + t:
+      1. ant a starts at (a + g) % n (spread_starts) or 0 and runs sampled_walk on tau * H with the uniforms u[t,a];
+      2. its cost is that of its tour rotated to start at node 0, summed left to right;
+      3. a refused walk, a cost that is not finite or a smallest cost not > 0 ends the run: status ACO_STATUS_BAD_WEIGHTS,
+         iters_done = t, tau and the best pair as they were;
+      4. ib = the first cheapest ant, trace[t] = cost[ib], the best pair is replaced iff cost[ib] < best_cost;
+      5. X = the best tour if gb_every > 0 and (g + 1) % gb_every == 0 else ant ib's; every off-diagonal entry: tau * (1 - rho),
+         + 1 / cost(X) on X's edges (both directions), clamped into [tau_max * min_ratio, tau_max], tau_max = 1 / (rho * best_cost).
+    u [iters,ants,n-1] uniforms in [0,1), or None: philox_uniforms(seed, 1, iters * ants, n - 1, b0=b, k0=iter0 * ants, c3=2)
+    reshaped, the draws the device makes for instance b of a batch.  min_ratio None = 1 / (2 n).  -> a namespace with tau,
+    best_tour (list or None), best_cost, trace (list), iters_done, status, ant_tours [ants,n+1] int32 (rotated; -1 rows for
+    refused walks) and ant_cost [ants] (NaN for those) of the last iteration whose walks ran (None when iters = 0)."""
+    import types
+
+    import numpy as np
+    D, H = np.asarray(D, dtype=np.float64), np.asarray(H, dtype=np.float64)
+    n = D.shape[0]
+    R, K, iter0 = int(ants), int(iters), int(iter0)
+    assert 3 <= n <= ACO_MAX_N and 1 <= R <= ACO_MAX_ANTS and K >= 0 and iter0 >= 0 and (iter0 + K) * R < 2 ** 32
+    assert 0 < rho < 1 and gb_every >= 0
+    min_ratio = np.float64(1.0 / (2 * n) if min_ratio is None else min_ratio)
+    assert 0 < min_ratio <= 1
+    rho = np.float64(rho)
+    if u is None:
+        u = philox_uniforms(seed, 1, K * R, n - 1, b0=b, k0=iter0 * R, c3=2)
+    u = np.asarray(u, dtype=np.float64).reshape(K, R, n - 1)
+    tau = aco_init_tau(D, rho) if tau is None else np.array(tau, dtype=np.float64)
+    best = None if best_tour is None else [int(v) for v in best_tour]
+    best_cost = np.float64(np.inf if best_cost is None else best_cost)
+    keep = np.float64(1.0) - rho
+    off = ~np.eye(n, dtype=bool)
+    trace, status, done, ant_tours, ant_cost = [], 0, K, None, None
+    with np.errstate(all="ignore"):
+        for t in range(K):
+            g = iter0 + t
+            W = tau * H
+            tours, ant_tours, ant_cost = [], np.full((R, n + 1), -1, dtype=np.int32), np.full(R, np.nan)
+            for a in range(R):
+                w = sampled_walk(W, (a + g) % n if spread_starts else 0, u[t, a])
+                if w is not None:
+                    z = w.index(0)
+                    w = w[z:n] + w[:z] + [0]
+                    c = np.float64(0.0)
+                    for x, y in zip(w[:-1], w[1:]):
+                        c = c + D[x, y]
+                    ant_tours[a], ant_cost[a] = w, c
+                tours.append(w)
+            if any(w is None for w in tours) or not np.isfinite(ant_cost).all() or not ant_cost.min() > 0:
+                status, done = ACO_STATUS_BAD_WEIGHTS, t
+                break
+            ib = int(np.argmin(ant_cost))
+            trace.append(ant_cost[ib])
+            if ant_cost[ib] < best_cost:
+                best, best_cost = tours[ib], ant_cost[ib]
+            gb = gb_every > 0 and (g + 1) % gb_every == 0
+            X, xc = (best, best_cost) if gb else (tours[ib], ant_cost[ib])
+            q = np.float64(1.0) / xc
+            tau_max = np.float64(1.0) / (rho * best_cost)
+            tau_min = tau_max * min_ratio
+            on = np.zeros((n, n), dtype=bool)
+            on[X[:-1], X[1:]] = True
+            on[X[1:], X[:-1]] = True
+            v = tau * keep
+            v = np.where(on, v + q, v)
+            v = np.where(v < tau_min, tau_min, v)
+            v = np.where(v > tau_max, tau_max, v)
+            tau = np.where(off, v, tau)
+    return types.SimpleNamespace(tau=tau, best_tour=best, best_cost=best_cost, trace=trace, iters_done=done, status=status,
+                                 ant_tours=ant_tours, ant_cost=ant_cost)
+
+
 def fixed_edge_tour(G, e, scale=None, lkh_path=None, base_tour=None, label_iters=None, perturbation_moves=None, **kwargs):
     """A tour of G that holds edge e (reference __init__.py:63-79: LKH with e fixed).  Here: the fixed-edge search of
     gnngls_amd.labels on the device -- guided_local_search on G's weights with e's weight lowered by M, guide = those weights,

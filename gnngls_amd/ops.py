@@ -620,6 +620,110 @@ def guided_or_opt(tour, cost, D, guides, outer_iters, k=None, penalty=None, pert
     return r
 
 
+ACO_MAX_N = 1024                                              # GNNGLS_ACO_MAX_N
+ACO_MAX_ANTS = 256                                            # GNNGLS_ACO_MAX_ANTS
+
+
+@dataclass
+class AcoResult:
+    best_tour: torch.Tensor      # [B,n+1] int32, closed at node 0
+    best_cost: torch.Tensor      # [B] fp64 (+inf: no tour yet)
+    tau: torch.Tensor            # [B,n,n] fp64 the pheromone after the run (the caller's tensor when one was given)
+    iters_done: torch.Tensor     # [B] int32 completed iterations
+    status: torch.Tensor         # [B] int32 STATUS_OK or (aco_launch only) SAMPLE_BAD_WEIGHTS
+    trace_cost: torch.Tensor     # [B,iters] fp64 the iteration-best cost (NaN: the iteration never completed), or None
+    ant_tours: torch.Tensor      # [B,ants,n+1] int32 the ants of the last iteration whose walks ran, or None
+    ant_cost: torch.Tensor       # [B,ants] fp64, or None
+
+
+def aco_heuristic(G, beta=2.0, kind="inverse"):
+    """The heuristic matrix H of aco from an edge score G [B,n,n] where SMALLER is better, in fp64 on G's device (host.aco_heuristic
+    is the same in NumPy).  kind 'inverse': G ** -beta, the classical 1 / d.  kind 'shifted', for scores that reach 0 or below
+    (regret predictions, alpha): ((G - min) / (mean - min) + 0.1) ** -beta with min and mean over the off-diagonal entries of each
+    instance.  The diagonal is 0.  A score that is constant over an instance has mean == min: its shifted H is 0 / 0 = NaN, which
+    aco refuses (such a score says nothing; use torch.ones_like for a heuristic-free run)."""
+    G = G.to(torch.float64)
+    n = G.shape[-1]
+    off = ~torch.eye(n, dtype=torch.bool, device=G.device)
+    if kind == "inverse":
+        H = G ** -float(beta)
+    elif kind == "shifted":
+        lo = torch.where(off, G, torch.full_like(G, float("inf"))).amin(dim=(-2, -1), keepdim=True)
+        mean = torch.where(off, G, torch.zeros_like(G)).sum(dim=(-2, -1), keepdim=True) / (n * (n - 1))
+        H = ((G - lo) / (mean - lo) + 0.1) ** -float(beta)
+    else:
+        raise ValueError(f"aco_heuristic: unknown kind {kind!r} ('inverse' or 'shifted')")
+    return torch.where(off, H, torch.zeros_like(H)).contiguous()
+
+
+def aco_init_tau(D, rho):
+    """The start pheromone of aco, [B,n,n] fp64: every entry 1 / (rho * the cost of the instance's nearest-neighbour tour), the
+    tau_max of a best tour of that cost."""
+    B, n, n2 = D.shape
+    assert n == n2 and D.dtype == torch.float64
+    cost = tour_cost(nearest_neighbor(D), D)
+    return (1.0 / (float(rho) * cost))[:, None, None].expand(B, n, n).contiguous()
+
+
+def aco_launch(D, H, ants=16, iters=100, rho=0.1, min_ratio=None, gb_every=0, spread_starts=True, seed=0, u=None, iter0=0, tau=None,
+               best_tour=None, best_cost=None, want_trace=False, want_ants=False):
+    """The launch behind aco and torch.ops.gnngls.aco: -> AcoResult, nothing raised for an instance whose run met bad weights (its
+    status is SAMPLE_BAD_WEIGHTS, its iters_done the iterations it completed)."""
+    _dev()
+    B, n, n2 = D.shape
+    assert n == n2 and D.dtype == torch.float64
+    assert H.shape == D.shape and H.dtype == torch.float64, f"H shape {tuple(H.shape)} / dtype does not match D [{B},{n},{n}] fp64"
+    dev = D.device
+    ants, iters, iter0 = int(ants), int(iters), int(iter0)
+    if min_ratio is None:
+        min_ratio = 1.0 / (2 * n)
+    if u is not None:
+        u = u.to(device=dev, dtype=torch.float64).contiguous()
+        assert u.shape == (B, iters, ants, n - 1), f"u shape {tuple(u.shape)} is not [{B},{iters},{ants},{n - 1}]"
+    if tau is None:
+        tau = aco_init_tau(D, rho)
+    assert tau.dtype == torch.float64 and tau.shape == (B, n, n) and tau.is_contiguous() and tau.device == dev, \
+        f"tau must be a contiguous fp64 [{B},{n},{n}] tensor on D's device (it is updated in place)"
+    best_tour = torch.zeros((B, n + 1), dtype=torch.int32, device=dev) if best_tour is None else best_tour.to(dev).contiguous().clone()
+    best_cost = torch.full((B,), float("inf"), dtype=torch.float64, device=dev) if best_cost is None else best_cost.to(dev).contiguous().clone()
+    assert best_tour.dtype == torch.int32 and best_tour.shape == (B, n + 1), f"best_tour shape {tuple(best_tour.shape)} is not [{B},{n + 1}]"
+    assert best_cost.dtype == torch.float64 and best_cost.shape == (B,), f"best_cost shape {tuple(best_cost.shape)} is not [{B}]"
+    iters_done, status = (torch.zeros((B,), dtype=torch.int32, device=dev) for _ in range(2))
+    trace = torch.full((B, max(iters, 0)), float("nan"), dtype=torch.float64, device=dev) if want_trace else None
+    ant_tours = torch.full((B, max(ants, 0), n + 1), -1, dtype=torch.int32, device=dev) if want_ants else None
+    ant_cost = torch.full((B, max(ants, 0)), float("nan"), dtype=torch.float64, device=dev) if want_ants else None
+    L = _lib.load()
+    if not hasattr(L, "gnngls_aco_run"):
+        raise _lib.GnnglsHipError("this build of libgnngls_hip.so has no gnngls_aco_run")
+    _lib.check(L.gnngls_aco_run(_lib.ptr(D.contiguous()), _lib.ptr(H.contiguous()), _lib.ptr(tau), _lib.ptr(best_tour), _lib.ptr(best_cost),
+                                B, n, ants, iters, iter0, float(rho), float(min_ratio), int(gb_every), int(bool(spread_starts)),
+                                ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _lib.ptr(u), _lib.ptr(iters_done), _lib.ptr(status),
+                                _lib.ptr(trace), _lib.ptr(ant_tours), _lib.ptr(ant_cost), _lib.current_stream()), "aco_run")
+    return AcoResult(best_tour, best_cost, tau, iters_done, status, trace, ant_tours, ant_cost)
+
+
+def aco(D, H, ants=16, iters=100, rho=0.1, min_ratio=None, gb_every=0, spread_starts=True, seed=0, u=None, iter0=0, tau=None,
+        best_tour=None, best_cost=None, want_trace=False, want_ants=False):
+    """A MAX-MIN ant system (Stuetzle & Hoos) of a batch in ONE launch, one workgroup per instance, n <= ACO_MAX_N: `iters` times
+    { `ants` sampled walks on tau * H; the cheapest ant (every gb_every-th iteration: the best tour so far) deposits 1 / cost on its
+    edges after tau * (1 - rho); tau is clamped into [tau_max * min_ratio, tau_max], tau_max = 1 / (rho * best_cost) }
+    (include/gnngls_hip.h states the definition; host.aco restates it in NumPy, bit for bit).
+    D [B,n,n] fp64 costs; H [B,n,n] fp64 heuristic, larger = more attractive (aco_heuristic builds one from a distance, a regret
+    prediction or alpha).  min_ratio None = 1 / (2 n).  spread_starts: ant a of iteration g starts at (a + g) % n, else at node 0.
+    u [B,iters,ants,n-1] fp64 gives the uniforms (the run is then pinned bit for bit); None draws them on the device from Philox
+    under `seed`.  tau [B,n,n] fp64 is updated IN PLACE (None: aco_init_tau(D, rho)).  A run continues an earlier one from its
+    .tau, .best_tour and .best_cost with iter0 = that run's iterations, exactly.  -> AcoResult.  Weights that are no probabilities
+    (NaN, negative), or costs that are not finite and positive, raise."""
+    r = aco_launch(D, H, ants, iters, rho, min_ratio, gb_every, spread_starts, seed, u, iter0, tau, best_tour, best_cost, want_trace,
+                   want_ants)
+    bad = (r.status != 0).nonzero().flatten().tolist()
+    if bad:
+        raise ValueError(f"aco: instances {bad[:8]} met weights tau * H that are no probabilities (NaN, negative, infinite) or tour costs "
+                         f"that are not finite and positive, after {r.iters_done[bad[:8]].tolist()} iterations (status "
+                         f"{SAMPLE_BAD_WEIGHTS}): probabilities do not sum to 1")
+    return r
+
+
 def gls_run(D, guides, init_tour, init_cost, perturbation_moves=30, first_improvement=False,
             max_outer_iters=-1, time_limit_s=0.0, watchdog_s=None, trace_cap=0, want_trace_time=False,
             want_penalty=False, penalty_bits=0, retry_overflow=True, imp_cap=0, retry_asymmetric=True):

@@ -1,7 +1,7 @@
 """PyTorch-ROCm custom operators of the hot path: `torch.ops.gnngls.*` (north_star).
 
 Ten operators and, since the Or-opt descent, iterated local search, the 3-opt descent and guided local search over Or-opt, an
-eleventh to a fourteenth are registered with
+eleventh to a fourteenth, and with the ant system a fifteenth, are registered with
 `torch.library` over the C ABI of libgnngls_hip.so (include/gnngls_hip.h).  Each has
 exactly ONE implementation, for the CUDA dispatch key (= HIP on ROCm): there is no CPU kernel behind any of them, so
 calling one with CPU tensors fails in the dispatcher ("no CPU fallback" is structural, not a runtime check).  Shape
@@ -44,6 +44,12 @@ the current HIP stream, take caller-owned contiguous tensors and retain nothing.
         relocate's places); functional: the given penalties are copied, the counters after the run are returned; max_moves /
         max_steps <= 0 = the defaults of gnngls_amd.ops.guided_or_opt; status 3 as for or_opt_descent -- the op reports,
         gnngls_amd.ops.guided_or_opt raises
+    aco(D[B,n,n] f64, H[B,n,n] f64, ants, iters, iter0, rho, min_ratio, gb_every, spread_starts, seed, u[B,iters,ants,n-1] f64 or
+        None, tau[B,n,n] f64 or None, best_tour[B,n+1] i32 or None, best_cost[B] f64 or None) -> (best_tour, best_cost, tau,
+        iters_done[B] i32, status[B] i32, trace_cost[B,iters] f64, ant_tours[B,ants,n+1] i32, ant_cost[B,ants] f64): a MAX-MIN ant
+        system in one launch, n <= 1024, ants <= 256; functional: a given tau is copied, the pheromone after the run is returned;
+        min_ratio <= 0 = 1 / (2 n); status 6 marks an instance whose run met weights that are no probabilities -- the op reports,
+        gnngls_amd.ops.aco raises
 """
 import ctypes
 
@@ -71,6 +77,8 @@ _LIB.define("three_opt_descent(Tensor tour, Tensor cost, Tensor D, int max_moves
 _LIB.define("guided_or_opt(Tensor tour, Tensor cost, Tensor D, Tensor guides, int outer_iters, int iter0, Tensor? k, Tensor? penalty, "
             "int perturbation_moves, int max_seg, bool reverse, int max_moves, int max_steps, int trace_capacity) "
             "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+_LIB.define("aco(Tensor D, Tensor H, int ants, int iters, int iter0, float rho, float min_ratio, int gb_every, bool spread_starts, int seed, "
+            "Tensor? u, Tensor? tau, Tensor? best_tour, Tensor? best_cost) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
 
 _workspaces = {}      # device index -> uint8 scratch tensor for the forward (grown on demand, reused across calls)
 
@@ -176,6 +184,15 @@ def _guided_or_opt(tour, cost, D, guides, outer_iters, iter0, k, penalty, pertur
 _LIB.impl("guided_or_opt", _guided_or_opt, "CUDA")
 
 
+def _aco(D, H, ants, iters, iter0, rho, min_ratio, gb_every, spread_starts, seed, u, tau, best_tour, best_cost):
+    r = ops.aco_launch(D, H, ants, iters, rho, min_ratio if min_ratio > 0 else None, gb_every, spread_starts, seed, u, iter0,
+                       None if tau is None else tau.clone().contiguous(), best_tour, best_cost, want_trace=True, want_ants=True)
+    return r.best_tour, r.best_cost, r.tau, r.iters_done, r.status, r.trace_cost, r.ant_tours, r.ant_cost
+
+
+_LIB.impl("aco", _aco, "CUDA")
+
+
 # ---- shape functions (fake tensors / tracing); no arithmetic -------------------------------------------------------
 @torch.library.register_fake("gnngls::regret_forward")
 def _(feat, packed_weights, n, heads, head_dim, hidden, layers):
@@ -264,3 +281,12 @@ def _(tour, cost, D, guides, outer_iters, iter0, k, penalty, perturbation_moves,
     return (tour.new_empty(tuple(tour.shape)), cost.new_empty((B,)), tour.new_empty(tuple(tour.shape)), cost.new_empty((B,)), i32(), i32(),
             i32(), tour.new_empty((B, n, n), dtype=torch.int32), cost.new_empty((B, max(int(trace_capacity), 0)), dtype=torch.float64),
             i32())
+
+
+@torch.library.register_fake("gnngls::aco")
+def _(D, H, ants, iters, iter0, rho, min_ratio, gb_every, spread_starts, seed, u, tau, best_tour, best_cost):
+    B, n = D.shape[0], D.shape[1]
+    i32 = lambda: D.new_empty((B,), dtype=torch.int32)  # noqa: E731
+    return (D.new_empty((B, n + 1), dtype=torch.int32), D.new_empty((B,), dtype=torch.float64), D.new_empty((B, n, n), dtype=torch.float64),
+            i32(), i32(), D.new_empty((B, max(int(iters), 0)), dtype=torch.float64),
+            D.new_empty((B, max(int(ants), 0), n + 1), dtype=torch.int32), D.new_empty((B, max(int(ants), 0)), dtype=torch.float64))

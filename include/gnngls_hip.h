@@ -408,6 +408,46 @@ int gnngls_three_opt_lds_max_n(void);
 int gnngls_sample_nn_tours(const double *W, int B, int n, int R, int depot, int invert, uint64_t seed, const double *u,
                            int32_t *tours, int32_t *status, void *stream);
 
+/* ---- ant colony optimisation: a MAX-MIN ant system (Stuetzle & Hoos) over any edge heuristic ----------------------------------
+ * The second established use of an edge score beside the utility of guided local search: sample tours from it and reinforce
+ * what the good samples share.  The reference has no counterpart.  Definition (the contract; gnngls_amd.host.aco restates it in
+ * NumPy, bit for bit).  Per instance: D [n,n] fp64 the costs; H [n,n] fp64 the heuristic, larger = more attractive (the
+ * diagonal is never read as a candidate); tau [n,n] fp64 the pheromone, IN/OUT; best_tour [n+1] int32 and best_cost fp64, IN/OUT
+ * (best_cost = +inf: no tour yet; with a finite best_cost the tour's entries must be node ids).  Every fp64 operation is one add,
+ * multiply or divide, rounded once.  For t = 0 .. iters-1, with the global index g = iter0 + t:
+ *   1. Walks.  Ant a = 0 .. ants-1 starts at s = (a + g) mod n if spread_starts, else at node 0, and runs the walk of
+ *      gnngls_sample_nn_tours with depot s and invert = 0 on the weights w_j = tau[i,j] * H[i,j] (one multiply per candidate, formed
+ *      when row i is read): the same candidate order, inf rule, all-zero rule, refusal rule, summation order, x = u * total and
+ *      pick rule.  Uniforms: the caller's u[b,t,a,:], or Philox4x32-10 under the same key and 53-bit formula with counter
+ *      (b, g * ants + a, step, 2) -- counter word 3 = 2 keeps the stream apart from the walks' (0) and the kicks' (1).
+ *   2. Cost.  The closed walk is rotated so that node 0 is first and last, direction kept; its cost is the sum gnngls_tour_cost
+ *      computes for that rotated tour, in the same order (so gnngls_tour_cost of best_tour reproduces best_cost bit for bit).
+ *   3. Early end.  If any walk of the iteration met refused weights, any ant's cost is not finite, or the smallest cost is not
+ *      > 0, the instance's run ends here: status = GNNGLS_SAMPLE_BAD_WEIGHTS, iters_done = t, tau and the best pair as iteration
+ *      t-1 left them, trace_cost[t..] untouched.  Other instances are unaffected.
+ *   4. Selection.  ib = the lowest ant index among the minimal costs; trace_cost[t] = cost[ib]; the best pair is replaced only if
+ *      cost[ib] < best_cost.
+ *   5. Update.  The deposit tour X is the best tour so far if gb_every > 0 and (g + 1) % gb_every == 0, else ant ib's tour, and
+ *      cost(X) the cost held with it.  q = 1.0 / cost(X); keep = 1.0 - rho; tau_max = 1.0 / (rho * best_cost) with the best cost
+ *      after step 4; tau_min = tau_max * min_ratio.  For every ordered pair i != j: v = tau[i,j] * keep; if {i,j} is an edge of
+ *      X: v = v + q; if v < tau_min: v = tau_min; if v > tau_max: v = tau_max; tau[i,j] = v.  The diagonal is never written.  The
+ *      update is entry-wise (no reduction order), and a symmetric tau stays bitwise symmetric.
+ * After the loop iters_done = iters and status = 0.  Chaining: K1 iterations, then K2 with iter0 = K1 fed with the first run's
+ * tau, best_tour and best_cost, is the run of K1 + K2 iterations, bit for bit.
+ *   D, H, tau [B,n,n]; best_tour [B,n+1]; best_cost [B]; u [B,iters,ants,n-1] or NULL; iters_done, status [B] int32;
+ *   trace_cost [B,iters] or NULL; ant_tours [B,ants,n+1] int32 and ant_cost [B,ants] fp64, both or neither: the rotated tours and
+ *   costs of the ants of the last iteration whose walks ran (an early-ended one included; an ant that met refused weights has a
+ *   row of -1 and the cost NaN), untouched when iters = 0.
+ * One workgroup of min(ants, 16) wavefronts per instance runs all iterations of the launch; ant a walks on wavefront a % 16.
+ * 3 <= n <= GNNGLS_ACO_MAX_N, 1 <= ants <= GNNGLS_ACO_MAX_ANTS (beyond: GNNGLS_ERR_UNSUPPORTED); B >= 1, iters >= 0, iter0 >= 0,
+ * 0 < rho < 1, 0 < min_ratio <= 1, gb_every >= 0, (iter0 + iters) * ants < 2^32, no NULL pointer other than u, trace_cost and the
+ * ant pair (GNNGLS_ERR_ARG): rejected on the host, with a message, before any device work. */
+#define GNNGLS_ACO_MAX_N 1024
+#define GNNGLS_ACO_MAX_ANTS 256
+int gnngls_aco_run(const double *D, const double *H, double *tau, int32_t *best_tour, double *best_cost, int B, int n, int ants, int iters,
+                   int64_t iter0, double rho, double min_ratio, int gb_every, int spread_starts, uint64_t seed, const double *u,
+                   int32_t *iters_done, int32_t *status, double *trace_cost, int32_t *ant_tours, double *ant_cost, void *stream);
+
 /* Host-side query (oracle/one_tree.c has no counterpart; scripts/bench_bounds.py reports it): the launch gnngls_one_tree_bound makes
  * for n nodes -- *threads workgroup size (64 = one wavefront per instance, n <= 256), *lds_bytes dynamic LDS per workgroup,
  * *nodes_per_lane register slots per lane.  Any output pointer may be NULL. */
