@@ -45,6 +45,8 @@ SIGNATURES = {
     "gnngls_three_opt_lds_max_n": [],
     "gnngls_sample_nn_tours": [_vp, _int, _int, _int, _int, _int, _u64, _vp, _vp, _vp, _vp],
     "gnngls_aco_run": [_vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _i64, _f64, _f64, _int, _int, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gnngls_beam_search_workspace_bytes": [_int, _int, _int],
+    "gnngls_beam_search": [_vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "gnngls_gls_run": [_vp, _vp, _int, _int, _int, _vp, _vp, _int, _int, _int, _i64, _f64, _f64,
                        _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp],
     "gnngls_model_packed_floats": [_int, _int],
@@ -105,7 +107,8 @@ _RESTYPES = {"gnngls_last_error": ctypes.c_char_p, "gnngls_model_packed_floats":
              "gnngls_regret_prepared_bytes": ctypes.c_int64,
              "gnngls_regret_train_workspace_bytes": ctypes.c_int64,
              "gnngls_regret_forward_workspace_bytes_heads": ctypes.c_int64,
-             "gnngls_regret_train_workspace_bytes_heads": ctypes.c_int64}
+             "gnngls_regret_train_workspace_bytes_heads": ctypes.c_int64,
+             "gnngls_beam_search_workspace_bytes": ctypes.c_int64}
 
 _ABI4 = ("gnngls_regret_prepared_bytes", "gnngls_regret_prepare", "gnngls_regret_forward_prepared")
 # head counts other than 8 (an older build named by GNNGLS_HIP_SO lacks them; the 8-head path never calls them)
@@ -130,6 +133,8 @@ _THREE_OPT = ("gnngls_three_opt_best_move", "gnngls_three_opt_descent", "gnngls_
 _GUIDED_OR_OPT = ("gnngls_or_opt_o2a", "gnngls_guided_or_opt_run")
 # the ant system (an older build named by GNNGLS_HIP_SO lacks it; ops.aco then raises)
 _ACO = ("gnngls_aco_run",)
+# beam search (an older build named by GNNGLS_HIP_SO lacks it; ops.beam_search then raises)
+_BEAM = ("gnngls_beam_search", "gnngls_beam_search_workspace_bytes")
 _lib = None
 
 
@@ -152,7 +157,7 @@ def load():
         import torch  # noqa: F401
         L = ctypes.CDLL(SO)
         for name, argtypes in SIGNATURES.items():
-            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS or name in _BOUNDS or name in _SAMPLING or name in _ALPHA or name in _OR_OPT or name in _ILS or name in _THREE_OPT or name in _GUIDED_OR_OPT or name in _ACO) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
+            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS or name in _BOUNDS or name in _SAMPLING or name in _ALPHA or name in _OR_OPT or name in _ILS or name in _THREE_OPT or name in _GUIDED_OR_OPT or name in _ACO or name in _BEAM) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
                 continue              # an older build of the library named by GNNGLS_HIP_SO (same-box A/B of kernel variants)
             f = getattr(L, name)      # AttributeError if the symbol is missing
             f.argtypes = argtypes

@@ -2,6 +2,7 @@
 `insertion`, `local_search`, `guided_local_search` with the reference's signatures, return values and side
 effects, executed by the HIP kernels (the persistent search kernel, the one-launch insertion constructor).
 `alpha_nearness` (no counterpart in the reference) writes a model-free guide attribute for guided_local_search;
+`beam_search` (no counterpart either) decodes a tour from an edge attribute by beam search;
 `or_opt_descent` (no counterpart either) is local_search with Or-opt in relocate's place, `iterated_local_search` is that
 descent inside a loop of double-bridge kicks, and `three_opt_descent` is local_search with the exhaustive 3-opt scan in relocate's
 place.
@@ -112,6 +113,16 @@ def alpha_nearness(G, weight="weight", attr="alpha", max_iters=2000):
     A = ops.alpha_nearness(D, pi)[0].cpu().numpy()
     nx.set_edge_attributes(G, {(u, v): float(A[u, v]) for u, v in G.edges}, attr)
     return G
+
+
+def beam_search(G, depot, width, guide='regret_pred', weight='weight', select='cost'):
+    """A tour of G decoded from the edge attribute `guide` (smaller = better: a regret prediction, alpha, a distance, -log p) by beam
+    search of `width` paths from `depot` on the GPU (ops.beam_search; no counterpart in the reference, whose paper compares against
+    this decoder).  select 'cost': the shortest of the final beams on `weight`; 'score': the beam of the least summed guide.
+    width = 1 is the greedy decode, nearest_neighbor(G, depot, weight=guide) where the partial sums are exact."""
+    S = ops.as_dev(_attr_matrix(G, guide)[None], torch.float64)
+    D = S if weight == guide else ops.as_dev(_attr_matrix(G, weight)[None], torch.float64)
+    return ops.beam_search(S, int(width), depot, D, select).best_tour[0].tolist()
 
 
 def _check_status(r, what):

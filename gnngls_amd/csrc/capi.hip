@@ -15,6 +15,7 @@
 #include "../../include/gnngls_hip.h"
 #include "aco_kernels.h"
 #include "alpha_kernels.h"
+#include "beam_kernels.h"
 #include "bounds_kernels.h"
 #include "constructors_kernels.h"
 #include "gls_kernels.h"
@@ -468,6 +469,45 @@ int gnngls_aco_run(const double *D, const double *H, double *tau, int32_t *best_
                                       spread_starts != 0, seed, u, iters_done, status, trace_cost, ant_tours, ant_cost,
                                       (hipStream_t)stream);
     return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "aco_run");
+}
+
+static_assert(GNNGLS_BEAM_MAX_N == gnngls::kBeamMaxN && GNNGLS_BEAM_MAX_WIDTH == gnngls::kBeamMaxWidth &&
+              GNNGLS_BEAM_BAD_SCORE == gnngls::kBeamStatusBadScore, "include/gnngls_hip.h and beam_kernels.h disagree");
+
+int64_t gnngls_beam_search_workspace_bytes(int B, int n, int width) {
+    if (B < 1 || n < 3 || n > GNNGLS_BEAM_MAX_N || width < 1 || width > GNNGLS_BEAM_MAX_WIDTH) return 0;
+    return (int64_t)gnngls::beam_workspace_bytes(B, n, width);
+}
+
+int gnngls_beam_search(const double *S, const double *D, int B, int n, int width, int depot, int select, int32_t *best_tour,
+                       double *best_score, double *best_cost, int32_t *n_beams, int32_t *status, int32_t *beam_tours,
+                       double *beam_score, double *beam_cost, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (B < 1) return fail(GNNGLS_ERR_ARG, "beam_search: B=%d must be >= 1", B);
+    if (n < 3) return fail(GNNGLS_ERR_ARG, "beam_search: n=%d must be >= 3", n);
+    if (n > GNNGLS_BEAM_MAX_N)
+        return fail(GNNGLS_ERR_UNSUPPORTED, "beam_search: n=%d exceeds the largest supported instance (n <= %d: a back-pointer packs the "
+                    "node into 10 bits)", n, GNNGLS_BEAM_MAX_N);
+    if (width < 1) return fail(GNNGLS_ERR_ARG, "beam_search: width=%d must be >= 1", width);
+    if (width > GNNGLS_BEAM_MAX_WIDTH)
+        return fail(GNNGLS_ERR_UNSUPPORTED, "beam_search: width=%d exceeds the widest supported beam (width <= %d)", width,
+                    GNNGLS_BEAM_MAX_WIDTH);
+    if (depot < 0 || depot >= n) return fail(GNNGLS_ERR_ARG, "beam_search: depot=%d must be in [0, %d)", depot, n);
+    if (select != GNNGLS_BEAM_SELECT_SCORE && select != GNNGLS_BEAM_SELECT_COST)
+        return fail(GNNGLS_ERR_ARG, "beam_search: select=%d must be %d (score) or %d (cost)", select, GNNGLS_BEAM_SELECT_SCORE,
+                    GNNGLS_BEAM_SELECT_COST);
+    if (select == GNNGLS_BEAM_SELECT_COST && !D) return fail(GNNGLS_ERR_ARG, "beam_search: select=cost needs the distances D");
+    if (!S || !best_tour || !best_score || !best_cost || !n_beams || !status)
+        return fail(GNNGLS_ERR_ARG, "beam_search: NULL pointer (S, best_tour, best_score, best_cost, n_beams, status)");
+    if ((beam_tours == nullptr) != (beam_score == nullptr) || (beam_tours == nullptr) != (beam_cost == nullptr))
+        return fail(GNNGLS_ERR_ARG, "beam_search: NULL pointer (beam_tours, beam_score and beam_cost are given together or not at all)");
+    const int64_t need = (int64_t)gnngls::beam_workspace_bytes(B, n, width);
+    if (!workspace || workspace_bytes < need)
+        return fail(GNNGLS_ERR_ARG, "beam_search: workspace of %lld bytes is too small (gnngls_beam_search_workspace_bytes(%d, %d, %d) = "
+                    "%lld)", workspace ? (long long)workspace_bytes : 0LL, B, n, width, (long long)need);
+    if (((uintptr_t)workspace & 15u) != 0) return fail(GNNGLS_ERR_ARG, "beam_search: the workspace must be 16-byte aligned");
+    hipError_t e = gnngls::launch_beam_search(S, D, B, n, width, depot, select, best_tour, best_score, best_cost, n_beams, status,
+                                              beam_tours, beam_score, beam_cost, workspace, (hipStream_t)stream);
+    return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "beam_search");
 }
 
 int gnngls_gls_run(const double *D, const double *guides, int n_guides, int B, int n,

@@ -735,6 +735,71 @@ def aco(D, H, ants=16, iters=100, rho=0.1, min_ratio=None, gb_every=0, spread_st
                                  ant_tours=ant_tours, ant_cost=ant_cost)
 
 
+BEAM_MAX_N, BEAM_MAX_WIDTH = 1024, 1024                   # GNNGLS_BEAM_MAX_N, GNNGLS_BEAM_MAX_WIDTH
+BEAM_STATUS_BAD_SCORE = 1                                 # GNNGLS_BEAM_BAD_SCORE
+
+
+def beam_search(S, width, depot=0, D=None, select="score"):
+    """Beam-search decoding of one instance in NumPy, the definition of include/gnngls_hip.h (gnngls_beam_search) restated -- what
+    gnngls_amd.ops.beam_search is compared against bit for bit.  S [n,n] fp64, smaller = better; D [n,n] fp64 or None.
+      step 0: one beam [depot] with c = 0.0;
+      step t = 1 .. n-1: every (beam k, node j not on it) has key = c_k + S[last_k, j] (one add; a zero is taken as +0.0); the
+        min(width, #candidates) smallest in (key, k, j) are the new beams, ranked in that order, c := key.  The keys are laid out
+        as a [beams, n] array, so a stable argsort of its flattening IS that order (only the keys up to the width-th smallest
+        value are sorted: a partition finds that value first);
+      close: score = c + S[last, depot], tour = path + [depot], cost = the left-to-right sum of D along the tour;
+      select 'score': the beam smallest in (score, rank); 'cost': smallest in (cost, rank), which needs D.
+    An off-diagonal entry of S that is not finite refuses the instance: status BEAM_STATUS_BAD_SCORE, n_beams = 0, best_tour -1,
+    NaN scores.  -> a namespace with best_tour [n+1] int32, best_score, best_cost (NaN without D), n_beams, status and all beams:
+    beam_tours [width,n+1] int32, beam_score, beam_cost [width], rows from n_beams on -1 / NaN."""
+    import types
+
+    import numpy as np
+    S = np.asarray(S, dtype=np.float64)
+    n, W, depot = S.shape[0], int(width), int(depot)
+    assert S.shape == (n, n) and 3 <= n <= BEAM_MAX_N and 1 <= W <= BEAM_MAX_WIDTH and 0 <= depot < n
+    assert select in ("score", "cost") and (select == "score" or D is not None), "select='cost' needs D"
+    beam_tours = np.full((W, n + 1), -1, dtype=np.int32)
+    beam_score, beam_cost = np.full(W, np.nan), np.full(W, np.nan)
+    if not np.isfinite(S[~np.eye(n, dtype=bool)]).all():
+        return types.SimpleNamespace(best_tour=np.full(n + 1, -1, dtype=np.int32), best_score=np.float64(np.nan), best_cost=np.float64(np.nan),
+                                     n_beams=0, status=BEAM_STATUS_BAD_SCORE, beam_tours=beam_tours, beam_score=beam_score, beam_cost=beam_cost)
+    c = np.zeros(1)
+    paths = np.full((1, 1), depot, dtype=np.int32)
+    visited = np.zeros((1, n), dtype=bool)
+    visited[0, depot] = True
+    with np.errstate(all="ignore"):
+        for t in range(1, n):
+            key = c[:, None] + S[paths[:, -1]]
+            key = np.where(key == 0.0, 0.0, key)
+            flat = np.where(visited, np.inf, key).ravel()
+            open_ = ~visited.ravel()
+            m = min(W, int(open_.sum()))
+            cut = np.partition(flat[open_], m - 1)[m - 1]
+            cand = np.flatnonzero(open_ & (flat <= cut))            # ascending k * n + j, i.e. (k, j)
+            cand = cand[np.argsort(flat[cand], kind="stable")][:m]
+            k, j = cand // n, cand % n
+            c = flat[cand]
+            paths = np.concatenate([paths[k], j[:, None].astype(np.int32)], axis=1)
+            visited = visited[k]
+            visited[np.arange(m), j] = True
+        nb = paths.shape[0]
+        score = c + S[paths[:, -1], depot]
+        score = np.where(score == 0.0, 0.0, score)
+        tours = np.concatenate([paths, np.full((nb, 1), depot, dtype=np.int32)], axis=1)
+        cost = np.full(nb, np.nan)
+        if D is not None:
+            D = np.asarray(D, dtype=np.float64)
+            cost = np.zeros(nb)
+            for p in range(n):                                       # tour_cost: c = 0; c += w, left to right
+                cost = cost + D[tours[:, p], tours[:, p + 1]]
+    v = cost if select == "cost" else score
+    best = min(range(nb), key=lambda r: (v[r], r))
+    beam_tours[:nb], beam_score[:nb], beam_cost[:nb] = tours, score, cost
+    return types.SimpleNamespace(best_tour=tours[best].copy(), best_score=score[best], best_cost=cost[best], n_beams=nb, status=0,
+                                 beam_tours=beam_tours, beam_score=beam_score, beam_cost=beam_cost)
+
+
 def fixed_edge_tour(G, e, scale=None, lkh_path=None, base_tour=None, label_iters=None, perturbation_moves=None, **kwargs):
     """A tour of G that holds edge e (reference __init__.py:63-79: LKH with e fixed).  Here: the fixed-edge search of
     gnngls_amd.labels on the device -- guided_local_search on G's weights with e's weight lowered by M, guide = those weights,

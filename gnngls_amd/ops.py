@@ -724,6 +724,80 @@ def aco(D, H, ants=16, iters=100, rho=0.1, min_ratio=None, gb_every=0, spread_st
     return r
 
 
+BEAM_MAX_N = 1024                                             # GNNGLS_BEAM_MAX_N
+BEAM_MAX_WIDTH = 1024                                         # GNNGLS_BEAM_MAX_WIDTH
+BEAM_BAD_SCORE = 1                                            # GNNGLS_BEAM_BAD_SCORE
+_BEAM_SELECT = {"score": 0, "cost": 1}                        # GNNGLS_BEAM_SELECT_*
+
+
+@dataclass
+class BeamResult:
+    best_tour: torch.Tensor      # [B,n+1] int32, closed at the depot (-1: the instance was refused)
+    best_score: torch.Tensor     # [B] fp64 the best beam's summed score
+    best_cost: torch.Tensor      # [B] fp64 its tour_cost on D (NaN without D)
+    n_beams: torch.Tensor        # [B] int32 final beams (below width only where the tree has fewer leaves; 0: refused)
+    status: torch.Tensor         # [B] int32 STATUS_OK or (beam_search_launch only) BEAM_BAD_SCORE
+    beam_tours: torch.Tensor     # [B,width,n+1] int32 every final beam by rank, rows from n_beams on -1, or None
+    beam_score: torch.Tensor     # [B,width] fp64 (NaN from n_beams on), or None
+    beam_cost: torch.Tensor      # [B,width] fp64 (NaN from n_beams on and without D), or None
+
+
+def beam_search_workspace_bytes(B, n, width):
+    """The device scratch gnngls_beam_search needs for a batch (back-pointers, a tour buffer, the visited bits beyond LDS)."""
+    L = _lib.load()
+    if not hasattr(L, "gnngls_beam_search"):
+        raise _lib.GnnglsHipError("this build of libgnngls_hip.so has no gnngls_beam_search")
+    return int(L.gnngls_beam_search_workspace_bytes(int(B), int(n), int(width)))
+
+
+def beam_search_launch(S, width, depot=0, D=None, select="score", want_beams=False, workspace=None):
+    """The launch behind beam_search and torch.ops.gnngls.beam_search: -> BeamResult, no synchronisation, nothing raised for a
+    refused instance (its status is BEAM_BAD_SCORE).  workspace: a uint8 device tensor of at least
+    beam_search_workspace_bytes(B, n, width) bytes to reuse across calls (None: allocated here)."""
+    dev = _dev()
+    B, n, n2 = S.shape
+    assert n == n2 and S.dtype == torch.float64
+    if select not in _BEAM_SELECT:
+        raise ValueError(f"beam_search: unknown select {select!r} ('score' or 'cost')")
+    if D is not None:
+        assert D.shape == S.shape and D.dtype == torch.float64, f"D shape {tuple(D.shape)} / dtype does not match S [{B},{n},{n}] fp64"
+        D = D.contiguous()
+    width, depot = int(width), int(depot)
+    L = _lib.load()
+    if not hasattr(L, "gnngls_beam_search"):
+        raise _lib.GnnglsHipError("this build of libgnngls_hip.so has no gnngls_beam_search")
+    if workspace is None:
+        workspace = torch.empty((max(int(L.gnngls_beam_search_workspace_bytes(B, n, width)), 16),), dtype=torch.uint8, device=dev)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.is_cuda, "workspace: a contiguous uint8 device tensor"
+    wb = max(width, 0)
+    best_tour = torch.empty((B, n + 1), dtype=torch.int32, device=dev)
+    best_score, best_cost = (torch.empty((B,), dtype=torch.float64, device=dev) for _ in range(2))
+    n_beams, status = (torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(2))
+    beam_tours = torch.empty((B, wb, n + 1), dtype=torch.int32, device=dev) if want_beams else None
+    beam_score, beam_cost = ((torch.empty((B, wb), dtype=torch.float64, device=dev) for _ in range(2)) if want_beams else (None, None))
+    _lib.check(L.gnngls_beam_search(_lib.ptr(S.contiguous()), _lib.ptr(D), B, n, width, depot, _BEAM_SELECT[select], _lib.ptr(best_tour),
+                                    _lib.ptr(best_score), _lib.ptr(best_cost), _lib.ptr(n_beams), _lib.ptr(status), _lib.ptr(beam_tours),
+                                    _lib.ptr(beam_score), _lib.ptr(beam_cost), _lib.ptr(workspace), ctypes.c_int64(workspace.numel()),
+                                    _lib.current_stream()), "beam_search")
+    return BeamResult(best_tour, best_score, best_cost, n_beams, status, beam_tours, beam_score, beam_cost)
+
+
+def beam_search(S, width, depot=0, D=None, select="score", want_beams=False, workspace=None):
+    """Beam-search decoding of a batch in ONE launch, one workgroup per instance, n <= BEAM_MAX_N, width <= BEAM_MAX_WIDTH: from
+    [depot], n - 1 times { every (beam k, unvisited node j) gets key = c_k + S[last_k, j]; the `width` smallest in (key, k, j)
+    are the new beams }, then every beam is closed with S[last, depot] (include/gnngls_hip.h states the definition;
+    host.beam_search restates it in NumPy, bit for bit).  S [B,n,n] fp64, smaller = better (distances, alpha, a regret
+    prediction, -log p); D [B,n,n] fp64 the distances or None.  select 'score': the beam of the least summed score; 'cost': the
+    shortest of the final beams on D.  width = 1 is the greedy decode.  -> BeamResult (want_beams: with every final beam).  An
+    instance whose S has an off-diagonal entry that is not finite raises."""
+    r = beam_search_launch(S, width, depot, D, select, want_beams, workspace)
+    bad = (r.status != 0).nonzero().flatten().tolist()
+    if bad:
+        raise ValueError(f"beam_search: instances {bad[:8]} have a score matrix with an off-diagonal entry that is NaN or infinite "
+                         f"(status {BEAM_BAD_SCORE})")
+    return r
+
+
 def gls_run(D, guides, init_tour, init_cost, perturbation_moves=30, first_improvement=False,
             max_outer_iters=-1, time_limit_s=0.0, watchdog_s=None, trace_cap=0, want_trace_time=False,
             want_penalty=False, penalty_bits=0, retry_overflow=True, imp_cap=0, retry_asymmetric=True):

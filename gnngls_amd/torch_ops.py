@@ -1,7 +1,7 @@
 """PyTorch-ROCm custom operators of the hot path: `torch.ops.gnngls.*` (north_star).
 
 Ten operators and, since the Or-opt descent, iterated local search, the 3-opt descent and guided local search over Or-opt, an
-eleventh to a fourteenth, and with the ant system a fifteenth, are registered with
+eleventh to a fourteenth, with the ant system a fifteenth and with beam search a sixteenth, are registered with
 `torch.library` over the C ABI of libgnngls_hip.so (include/gnngls_hip.h).  Each has
 exactly ONE implementation, for the CUDA dispatch key (= HIP on ROCm): there is no CPU kernel behind any of them, so
 calling one with CPU tensors fails in the dispatcher ("no CPU fallback" is structural, not a runtime check).  Shape
@@ -50,6 +50,11 @@ the current HIP stream, take caller-owned contiguous tensors and retain nothing.
         system in one launch, n <= 1024, ants <= 256; functional: a given tau is copied, the pheromone after the run is returned;
         min_ratio <= 0 = 1 / (2 n); status 6 marks an instance whose run met weights that are no probabilities -- the op reports,
         gnngls_amd.ops.aco raises
+    beam_search(S[B,n,n] f64, D[B,n,n] f64 or None, width, depot, select) -> (best_tour[B,n+1] i32, best_score[B] f64, best_cost[B] f64,
+        n_beams[B] i32, status[B] i32, beam_tours[B,width,n+1] i32, beam_score[B,width] f64, beam_cost[B,width] f64): beam-search
+        decoding from any edge score in one launch, n <= 1024, width <= 1024; select in {'score', 'cost'} ('cost' needs D);
+        rows from n_beams on are -1 / NaN; status 1 marks an instance whose score has an off-diagonal entry that is not finite
+        -- the op reports, gnngls_amd.ops.beam_search raises
 """
 import ctypes
 
@@ -79,6 +84,7 @@ _LIB.define("guided_or_opt(Tensor tour, Tensor cost, Tensor D, Tensor guides, in
             "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("aco(Tensor D, Tensor H, int ants, int iters, int iter0, float rho, float min_ratio, int gb_every, bool spread_starts, int seed, "
             "Tensor? u, Tensor? tau, Tensor? best_tour, Tensor? best_cost) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+_LIB.define("beam_search(Tensor S, Tensor? D, int width, int depot, str select) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
 
 _workspaces = {}      # device index -> uint8 scratch tensor for the forward (grown on demand, reused across calls)
 
@@ -193,6 +199,14 @@ def _aco(D, H, ants, iters, iter0, rho, min_ratio, gb_every, spread_starts, seed
 _LIB.impl("aco", _aco, "CUDA")
 
 
+def _beam_search(S, D, width, depot, select):
+    r = ops.beam_search_launch(S, width, depot, D, select, want_beams=True)
+    return r.best_tour, r.best_score, r.best_cost, r.n_beams, r.status, r.beam_tours, r.beam_score, r.beam_cost
+
+
+_LIB.impl("beam_search", _beam_search, "CUDA")
+
+
 # ---- shape functions (fake tensors / tracing); no arithmetic -------------------------------------------------------
 @torch.library.register_fake("gnngls::regret_forward")
 def _(feat, packed_weights, n, heads, head_dim, hidden, layers):
@@ -290,3 +304,12 @@ def _(D, H, ants, iters, iter0, rho, min_ratio, gb_every, spread_starts, seed, u
     return (D.new_empty((B, n + 1), dtype=torch.int32), D.new_empty((B,), dtype=torch.float64), D.new_empty((B, n, n), dtype=torch.float64),
             i32(), i32(), D.new_empty((B, max(int(iters), 0)), dtype=torch.float64),
             D.new_empty((B, max(int(ants), 0), n + 1), dtype=torch.int32), D.new_empty((B, max(int(ants), 0)), dtype=torch.float64))
+
+
+@torch.library.register_fake("gnngls::beam_search")
+def _(S, D, width, depot, select):
+    B, n, W = S.shape[0], S.shape[1], max(int(width), 0)
+    i32 = lambda: S.new_empty((B,), dtype=torch.int32)  # noqa: E731
+    f64 = lambda: S.new_empty((B,), dtype=torch.float64)  # noqa: E731
+    return (S.new_empty((B, n + 1), dtype=torch.int32), f64(), f64(), i32(), i32(), S.new_empty((B, W, n + 1), dtype=torch.int32),
+            S.new_empty((B, W), dtype=torch.float64), S.new_empty((B, W), dtype=torch.float64))

@@ -448,6 +448,44 @@ int gnngls_aco_run(const double *D, const double *H, double *tau, int32_t *best_
                    int64_t iter0, double rho, double min_ratio, int gb_every, int spread_starts, uint64_t seed, const double *u,
                    int32_t *iters_done, int32_t *status, double *trace_cost, int32_t *ant_tours, double *ant_cost, void *stream);
 
+/* ---- beam search: decode tours from any edge score ---------------------------------------------------------------------------
+ * The most common use of a learned edge score in GNN-for-TSP work: build a tour from the score directly, greedily (width 1) or
+ * keeping the `width` best partial paths.  The reference has no counterpart (its paper compares against these decoders).
+ * Definition (the contract; gnngls_amd.host.beam_search restates it in NumPy, bit for bit).  Per instance: S [n,n] fp64 a
+ * cost-like score, smaller = better (distances, alpha, regret predictions, -log p); optionally D [n,n] fp64 the distances.
+ *   State.  A beam is a path from `depot` with a score c; beams are ordered by rank k = 0, 1, ...  Step 0: one beam, [depot],
+ *      c = 0.0.
+ *   Step t = 1 .. n-1.  The candidates are all pairs (beam k, node j not on beam k's path) with key = c_k + S[last_k, j]: one
+ *      fp64 add, rounded once, and a key that is zero is taken as +0.0.  The new beams are the min(width, #candidates) candidates
+ *      smallest in the total order (key, k, j) -- keys compare as fp64 values, ties go to the lower k, then to the lower j --
+ *      ranked in that order, with c := key.  Nothing is deduplicated: two beams may hold the same node set.
+ *   Close.  Every final beam gets score = c + S[last, depot] (a zero again taken as +0.0) and the tour path + [depot].  n_beams is
+ *      the number of final beams; it is below width only where the tree has fewer leaves.  Given D, a beam's cost is what
+ *      gnngls_tour_cost computes for its tour, in the same order and with the same bits.
+ *   Select.  GNNGLS_BEAM_SELECT_SCORE: the final beam smallest in (score, rank).  GNNGLS_BEAM_SELECT_COST: the one smallest in
+ *      (cost, rank), the "shortest tour" decoder; it requires D (a NaN cost leaves the choice unspecified).
+ *   Refusal.  If any off-diagonal entry of S[b] is NaN or infinite, instance b gets status GNNGLS_BEAM_BAD_SCORE, n_beams = 0,
+ *      tours of -1 and NaN scores and costs; other instances are unaffected.  The diagonal is never read.
+ * Consequences: with width = 1 and scores whose partial sums are exact the tour is gnngls_nearest_neighbor's; with
+ * width >= (n-1)! the search is exhaustive and best_score is the minimum over all tours of the left-to-right summed score.
+ *   S [B,n,n]; D [B,n,n] or NULL; best_tour [B,n+1] int32; best_score, best_cost [B] fp64 (best_cost NaN without D); n_beams,
+ *   status [B] int32; beam_tours [B,width,n+1] int32, beam_score and beam_cost [B,width] fp64, all three or none: every final beam
+ *   by rank, rows from n_beams on -1 / NaN; workspace: device scratch of at least gnngls_beam_search_workspace_bytes(B, n, width)
+ *   bytes, 16-byte aligned (the back-pointers of every step, a tour buffer and, where they do not fit into LDS, the visited bits).
+ * One workgroup of min(width, 16) wavefronts per instance runs every step, the close and the selection in one launch.
+ * 3 <= n <= GNNGLS_BEAM_MAX_N and 1 <= width <= GNNGLS_BEAM_MAX_WIDTH (above: GNNGLS_ERR_UNSUPPORTED); B >= 1, 0 <= depot < n,
+ * select one of the two, D given for GNNGLS_BEAM_SELECT_COST, no NULL pointer other than D and the beam triple, a workspace
+ * large enough (GNNGLS_ERR_ARG): rejected on the host, with a message, before any device work. */
+#define GNNGLS_BEAM_MAX_N 1024
+#define GNNGLS_BEAM_MAX_WIDTH 1024
+#define GNNGLS_BEAM_SELECT_SCORE 0
+#define GNNGLS_BEAM_SELECT_COST 1
+#define GNNGLS_BEAM_BAD_SCORE 1
+int64_t gnngls_beam_search_workspace_bytes(int B, int n, int width);          /* 0 for arguments out of range */
+int gnngls_beam_search(const double *S, const double *D, int B, int n, int width, int depot, int select, int32_t *best_tour,
+                       double *best_score, double *best_cost, int32_t *n_beams, int32_t *status, int32_t *beam_tours,
+                       double *beam_score, double *beam_cost, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Host-side query (oracle/one_tree.c has no counterpart; scripts/bench_bounds.py reports it): the launch gnngls_one_tree_bound makes
  * for n nodes -- *threads workgroup size (64 = one wavefront per instance, n <= 256), *lds_bytes dynamic LDS per workgroup,
  * *nodes_per_lane register slots per lane.  Any output pointer may be NULL. */
