@@ -16,7 +16,9 @@ Parity status
   softmax over the in-edges of each destination -> sum_src a*ft[src]); two independent
   formulations (edge-list scatter over networkx's own nx.line_graph, and a dense masked
   softmax built from the closed-form "share exactly one endpoint" rule) must agree
-  (tests/test_model_oracle.py).
+  (tests/test_model_oracle.py).  A third, `gat_aggregate_stars` on a `CompleteLineGraph`, uses neither an arc list nor
+  networkx (dense blocks per star of K_n) and is what the GPU tests above n = 200 compare with; it is pinned to the
+  edge-list form in the same file.
 
 Graph convention: the GNN runs on the line graph of the complete TSP graph K_n
 (gnngls/datasets.py:56-60).  Line-graph node id = rank of the TSP edge (i<j) in
@@ -114,6 +116,88 @@ def batch_line_graphs(n, batch):
     return LineGraph(n, src, dst, g.ndata["e"].repeat(batch, 1))
 
 
+class CompleteLineGraph:
+    """The line graph of K_n (or the disjoint union of `batch` copies of it) WITHOUT an arc list: what GATConvOracle needs to
+    aggregate star by star (gat_aggregate_stars).  star[v] = line-graph ids of the n - 1 TSP edges at node v, by the other
+    endpoint; with a batch, star[b * n + v] holds the ids of instance b (offset b * N).  Every line-graph node {i, j} sits in
+    exactly two stars, i's and j's, and its in-neighbours are the other members of those two stars.
+    block_elems: logits ([stars, H, n-1, n-1]) one group of stars may hold at a time."""
+
+    def __init__(self, n, batch=1, block_elems=1 << 24):
+        self.n, self.batch, self.block_elems = n, batch, block_elems
+        e = np.array(edge_list(n), dtype=np.int64)
+        N = len(e)
+        rank = np.full((n, n), -1, dtype=np.int64)
+        rank[e[:, 0], e[:, 1]] = np.arange(N)
+        rank[e[:, 1], e[:, 0]] = np.arange(N)
+        star = rank[~np.eye(n, dtype=bool)].reshape(n, n - 1)                 # row v: {v, k} for k != v, ascending k
+        star = (star[None, :, :] + (np.arange(batch, dtype=np.int64) * N)[:, None, None]).reshape(batch * n, n - 1)
+        self.star = torch.from_numpy(star)
+        self.ndata = {"e": torch.from_numpy(e).repeat(batch, 1)}
+
+    def number_of_nodes(self):
+        return self.ndata["e"].shape[0]
+
+    def to(self, device):
+        return self
+
+
+def complete_line_graph(n, batch=1):
+    """The graph object of the large-n tests: same model outputs as line_graph_networkx(n) / batch_line_graphs(n, batch)
+    (tests/test_model_oracle.py), at n = 257 in seconds and at n = 423 at all."""
+    return CompleteLineGraph(n, batch)
+
+
+def _star_logits(el, er, idx, slope):
+    """[g, H, d, s] logits leaky_relu(el[s] + er[d]) over the stars idx [g, n-1]; s = d (a node is not its own in-neighbour)
+    at -inf."""
+    ns = idx.shape[1]
+    a = el[idx].permute(0, 2, 1)[:, :, None, :]                              # [g, H, 1, s]
+    b = er[idx].permute(0, 2, 1)[:, :, :, None]                              # [g, H, d, 1]
+    e = torch.nn.functional.leaky_relu(a + b, slope)
+    return e.masked_fill(torch.eye(ns, dtype=torch.bool), -math.inf)
+
+
+def _star_block(ft, el, er, m, idx, slope):
+    """One group of stars: per (star, destination, head) the sum of exp(e - m) over the star's other members and the same
+    weights times ft -- the destination's softmax is the two stars' sums added (gat_aggregate_stars)."""
+    p = torch.exp(_star_logits(el, er, idx, slope) - m[idx].permute(0, 2, 1)[:, :, :, None])     # [g, H, d, s]
+    num = torch.matmul(p, ft[idx].permute(0, 2, 1, 3))                       # [g, H, d, s] x [g, H, s, F]
+    return p.sum(dim=3).permute(0, 2, 1), num.permute(0, 2, 1, 3)            # [g, d, H], [g, d, H, F]
+
+
+def gat_aggregate_stars(ft, el, er, graph, slope=0.2):
+    """Formulation C, for the line graph of K_n only: destination {i, j} has the in-neighbours {i, k} and {k, j}, k not in
+    {i, j} -- the other members of the star of i and of the star of j.  Per star the logits are a dense [n-1, n-1] block per
+    head; a first pass takes every destination's maximum over both of its stars (detached: the softmax does not depend on the
+    shift), a second accumulates exp(e - m), its sum and p @ ft[star] into the destinations by index_add.  No arc list and no
+    [E, H, F] message tensor: n = 423 (75 million arcs) is 14 s per fp64 layer.  Under autograd every group of stars is a
+    torch.utils.checkpoint segment, so a training step of n = 257 keeps one group's blocks alive at a time."""
+    N, H, F = ft.shape
+    star = graph.star
+    ns = star.shape[1]
+    assert N == graph.number_of_nodes() and ns >= 2
+    g = max(1, graph.block_elems // (ns * ns * H))
+    groups = [star[a:a + g] for a in range(0, star.shape[0], g)]
+    with torch.no_grad():
+        m = torch.full((N, H), -math.inf, dtype=ft.dtype)
+        for idx in groups:
+            part = _star_logits(el, er, idx, slope).amax(dim=3).permute(0, 2, 1)               # [g, d, H]
+            m.scatter_reduce_(0, idx.reshape(-1, 1).expand(-1, H), part.reshape(-1, H), reduce="amax", include_self=True)
+    ckpt = torch.is_grad_enabled() and (ft.requires_grad or el.requires_grad or er.requires_grad)
+    z = torch.zeros((N, H), dtype=ft.dtype)
+    out = torch.zeros((N, H, F), dtype=ft.dtype)
+    for idx in groups:
+        if ckpt:
+            from torch.utils.checkpoint import checkpoint
+            s, num = checkpoint(_star_block, ft, el, er, m, idx, slope, use_reentrant=False)
+        else:
+            s, num = _star_block(ft, el, er, m, idx, slope)
+        z = z.index_add(0, idx.reshape(-1), s.reshape(-1, H))
+        out = out.index_add(0, idx.reshape(-1), num.reshape(-1, H, F))
+    return out / z[:, :, None]
+
+
 class GATConvOracle(nn.Module):
     """dgl.nn.GATConv(in_feats, out_feats, num_heads) as called at gnngls/models.py:23, DGL 0.6.1
     defaults: feat_drop=attn_drop=0, negative_slope=0.2, residual=False, activation=None, no bias.
@@ -142,7 +226,10 @@ class GATConvOracle(nn.Module):
         ft = self.fc(feat).view(-1, H, F)
         el = (ft * self.attn_l).sum(dim=-1)                      # [N,H]
         er = (ft * self.attn_r).sum(dim=-1)                      # [N,H]
-        rst = gat_aggregate_edge_list(ft, el, er, graph.src, graph.dst, self.negative_slope)
+        if isinstance(graph, CompleteLineGraph):
+            rst = gat_aggregate_stars(ft, el, er, graph, self.negative_slope)
+        else:
+            rst = gat_aggregate_edge_list(ft, el, er, graph.src, graph.dst, self.negative_slope)
         return rst if self.bias is None else rst + self.bias.view(1, H, F)
 
 
