@@ -47,6 +47,7 @@ SIGNATURES = {
     "gnngls_aco_run": [_vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _i64, _f64, _f64, _int, _int, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "gnngls_beam_search_workspace_bytes": [_int, _int, _int],
     "gnngls_beam_search": [_vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "gnngls_greedy_edge": [_vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "gnngls_gls_run": [_vp, _vp, _int, _int, _int, _vp, _vp, _int, _int, _int, _i64, _f64, _f64,
                        _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp],
     "gnngls_model_packed_floats": [_int, _int],
@@ -135,6 +136,8 @@ _GUIDED_OR_OPT = ("gnngls_or_opt_o2a", "gnngls_guided_or_opt_run")
 _ACO = ("gnngls_aco_run",)
 # beam search (an older build named by GNNGLS_HIP_SO lacks it; ops.beam_search then raises)
 _BEAM = ("gnngls_beam_search", "gnngls_beam_search_workspace_bytes")
+# greedy edge matching (an older build named by GNNGLS_HIP_SO lacks it; ops.greedy_edge then raises)
+_GREEDY_EDGE = ("gnngls_greedy_edge",)
 _lib = None
 
 
@@ -157,7 +160,7 @@ def load():
         import torch  # noqa: F401
         L = ctypes.CDLL(SO)
         for name, argtypes in SIGNATURES.items():
-            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS or name in _BOUNDS or name in _SAMPLING or name in _ALPHA or name in _OR_OPT or name in _ILS or name in _THREE_OPT or name in _GUIDED_OR_OPT or name in _ACO or name in _BEAM) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
+            if (name in _ABI4 or name in _HEADS or name in _CONSTRUCTORS or name in _BOUNDS or name in _SAMPLING or name in _ALPHA or name in _OR_OPT or name in _ILS or name in _THREE_OPT or name in _GUIDED_OR_OPT or name in _ACO or name in _BEAM or name in _GREEDY_EDGE) and "GNNGLS_HIP_SO" in os.environ and not hasattr(L, name):
                 continue              # an older build of the library named by GNNGLS_HIP_SO (same-box A/B of kernel variants)
             f = getattr(L, name)      # AttributeError if the symbol is missing
             f.argtypes = argtypes

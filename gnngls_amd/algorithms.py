@@ -2,7 +2,7 @@
 `insertion`, `local_search`, `guided_local_search` with the reference's signatures, return values and side
 effects, executed by the HIP kernels (the persistent search kernel, the one-launch insertion constructor).
 `alpha_nearness` (no counterpart in the reference) writes a model-free guide attribute for guided_local_search;
-`beam_search` (no counterpart either) decodes a tour from an edge attribute by beam search;
+`beam_search` (no counterpart either) decodes a tour from an edge attribute by beam search, `greedy_edge` by greedy edge matching;
 `or_opt_descent` (no counterpart either) is local_search with Or-opt in relocate's place, `iterated_local_search` is that
 descent inside a loop of double-bridge kicks, and `three_opt_descent` is local_search with the exhaustive 3-opt scan in relocate's
 place.
@@ -123,6 +123,16 @@ def beam_search(G, depot, width, guide='regret_pred', weight='weight', select='c
     S = ops.as_dev(_attr_matrix(G, guide)[None], torch.float64)
     D = S if weight == guide else ops.as_dev(_attr_matrix(G, weight)[None], torch.float64)
     return ops.beam_search(S, int(width), depot, D, select).best_tour[0].tolist()
+
+
+def greedy_edge(G, depot=0, guide='regret_pred', weight='weight'):
+    """A tour of G decoded from the edge attribute `guide` (smaller = better: a regret prediction, alpha, a distance, -log p) by greedy
+    edge matching on the GPU (ops.greedy_edge; no counterpart in the reference): the edges in ascending (guide, i, j), each accepted
+    if both ends have degree below 2 and it closes no subtour, the path closed at the end.  The tour starts and ends at `depot` and
+    leaves it towards the smaller-numbered neighbour.  `weight` only names the lengths the result's cost is summed on."""
+    S = ops.as_dev(_attr_matrix(G, guide)[None], torch.float64)
+    D = S if weight == guide else ops.as_dev(_attr_matrix(G, weight)[None], torch.float64)
+    return ops.greedy_edge(S, depot, D).tour[0].tolist()
 
 
 def _check_status(r, what):

@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 SO = os.path.join(HERE, "libgnngls_hip.so")
 SOURCES = ["gls_kernels.hip", "gls_plan.cpp", "model_kernels.hip", "model_plan.cpp", "train_kernels.hip", "heads_kernels.hip", "labels_kernels.hip", "constructors_kernels.hip",
-           "bounds_kernels.hip", "alpha_kernels.hip", "oropt_kernels.hip", "threeopt_kernels.hip", "sampling_kernels.hip", "aco_kernels.hip", "beam_kernels.hip", "capi.hip"]
+           "bounds_kernels.hip", "alpha_kernels.hip", "oropt_kernels.hip", "threeopt_kernels.hip", "sampling_kernels.hip", "aco_kernels.hip", "beam_kernels.hip", "greedy_edge_kernels.hip", "capi.hip"]
 # -ffp-contract=off: the guided matrix D + k*P (gnngls/algorithms.py:164) rounds twice and np.isclose
 # (operators.py:42) is evaluated literally; a fused multiply-add would change move selection.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result"]
@@ -39,7 +39,8 @@ HEADERS = {
     "sampling_kernels.hip": ["sampling_kernels.h", "philox.h"],
     "aco_kernels.hip": ["aco_kernels.h", "philox.h"],
     "beam_kernels.hip": ["beam_kernels.h"],
-    "capi.hip": ["aco_kernels.h", "beam_kernels.h", "gls_kernels.h", "gls_plan.h", "gls_policy.h", "model_kernels.h", "model_plan.h", "model_policy.h", "train_kernels.h", "heads_kernels.h",
+    "greedy_edge_kernels.hip": ["greedy_edge_kernels.h"],
+    "capi.hip": ["aco_kernels.h", "beam_kernels.h", "greedy_edge_kernels.h", "gls_kernels.h", "gls_plan.h", "gls_policy.h", "model_kernels.h", "model_plan.h", "model_policy.h", "train_kernels.h", "heads_kernels.h",
                  "labels_kernels.h", "constructors_kernels.h", "bounds_kernels.h", "alpha_kernels.h", "oropt_kernels.h", "threeopt_kernels.h", "sampling_kernels.h", os.path.join("..", "..", "include", "gnngls_hip.h")],
 }
 

@@ -19,6 +19,7 @@
 #include "bounds_kernels.h"
 #include "constructors_kernels.h"
 #include "gls_kernels.h"
+#include "greedy_edge_kernels.h"
 #include "heads_kernels.h"
 #include "labels_kernels.h"
 #include "model_kernels.h"
@@ -508,6 +509,23 @@ int gnngls_beam_search(const double *S, const double *D, int B, int n, int width
     hipError_t e = gnngls::launch_beam_search(S, D, B, n, width, depot, select, best_tour, best_score, best_cost, n_beams, status,
                                               beam_tours, beam_score, beam_cost, workspace, (hipStream_t)stream);
     return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "beam_search");
+}
+
+static_assert(GNNGLS_GREEDY_EDGE_MAX_N == gnngls::kGreedyEdgeMaxN && GNNGLS_GREEDY_EDGE_BAD_SCORE == gnngls::kGreedyEdgeStatusBadScore &&
+              GNNGLS_GREEDY_EDGE_STALLED == gnngls::kGreedyEdgeStatusStalled, "include/gnngls_hip.h and greedy_edge_kernels.h disagree");
+
+int gnngls_greedy_edge(const double *S, const double *D, int B, int n, int depot, int32_t *tour, double *score, double *cost,
+                       int32_t *edges, int32_t *rounds, int32_t *status, void *stream) {
+    if (B < 1) return fail(GNNGLS_ERR_ARG, "greedy_edge: B=%d must be >= 1", B);
+    if (n < 3) return fail(GNNGLS_ERR_ARG, "greedy_edge: n=%d must be >= 3", n);
+    if (n > GNNGLS_GREEDY_EDGE_MAX_N)
+        return fail(GNNGLS_ERR_ARG, "greedy_edge: n=%d exceeds the largest supported instance (n <= %d: one thread per node)", n,
+                    GNNGLS_GREEDY_EDGE_MAX_N);
+    if (depot < 0 || depot >= n) return fail(GNNGLS_ERR_ARG, "greedy_edge: depot=%d must be in [0, %d)", depot, n);
+    if (!S || !tour || !score || !cost || !rounds || !status)
+        return fail(GNNGLS_ERR_ARG, "greedy_edge: NULL pointer (S, tour, score, cost, rounds, status)");
+    hipError_t e = gnngls::launch_greedy_edge(S, D, B, n, depot, tour, score, cost, edges, rounds, status, (hipStream_t)stream);
+    return e == hipSuccess ? GNNGLS_OK : hip_fail(e, "greedy_edge");
 }
 
 int gnngls_gls_run(const double *D, const double *guides, int n_guides, int B, int n,

@@ -800,6 +800,153 @@ def beam_search(S, width, depot=0, D=None, select="score"):
                                  beam_tours=beam_tours, beam_score=beam_score, beam_cost=beam_cost)
 
 
+GREEDY_EDGE_MAX_N = 1024                                  # GNNGLS_GREEDY_EDGE_MAX_N
+GREEDY_EDGE_BAD_SCORE = 1                                 # GNNGLS_GREEDY_EDGE_BAD_SCORE
+
+
+def _greedy_edge_keys(S):
+    """-> (n, K) for greedy_edge: K[i, j] = K[j, i] = the key of {i, j} = S[min, max], a zero taken as +0.0; the diagonal +inf.
+    K is None where an off-diagonal entry of S is not finite."""
+    import numpy as np
+    S = np.asarray(S, dtype=np.float64)
+    n = S.shape[0]
+    assert S.shape == (n, n) and 3 <= n <= GREEDY_EDGE_MAX_N
+    if not np.isfinite(S[~np.eye(n, dtype=bool)]).all():
+        return n, None
+    K = np.triu(S, 1)
+    K = K + K.T
+    K = np.where(K == 0.0, 0.0, K)
+    K[np.diag_indices(n)] = np.inf
+    return n, K
+
+
+def _greedy_edge_result(n, K, D, depot, nbr, accepted, rounds):
+    """The closing edge, the tour from the depot and the two sums, from the n - 1 accepted edges (nbr: per node its neighbours)."""
+    import types
+
+    import numpy as np
+    e0, e1 = sorted(u for u in range(n) if len(nbr[u]) == 1)
+    nbr[e0].append(e1)
+    nbr[e1].append(e0)
+    edges = np.array(accepted + [(e0, e1)], dtype=np.int32)
+    tour, prev, cur = [depot], depot, min(nbr[depot])
+    for _ in range(n - 1):
+        tour.append(cur)
+        a, b = nbr[cur]
+        prev, cur = cur, (b if a == prev else a)
+    tour.append(depot)
+    tour = np.array(tour, dtype=np.int32)
+    score, cost = np.float64(0.0), np.float64(np.nan)
+    for p in range(n):
+        score = score + K[tour[p], tour[p + 1]]
+    if D is not None:
+        D = np.asarray(D, dtype=np.float64)
+        cost = np.float64(0.0)
+        for p in range(n):                                            # tour_cost: c = 0; c += w, left to right
+            cost = cost + D[tour[p], tour[p + 1]]
+    return types.SimpleNamespace(tour=tour, score=score, cost=cost, edges=edges, rounds=rounds, status=0)
+
+
+def _greedy_edge_refused(n):
+    import types
+
+    import numpy as np
+    return types.SimpleNamespace(tour=np.full(n + 1, -1, dtype=np.int32), score=np.float64(np.nan), cost=np.float64(np.nan),
+                                 edges=np.full((n, 2), -1, dtype=np.int32), rounds=0, status=GREEDY_EDGE_BAD_SCORE)
+
+
+def greedy_edge(S, depot=0, D=None):
+    """Greedy edge matching ("greedy merge") of one instance in NumPy, the definition of include/gnngls_hip.h (gnngls_greedy_edge)
+    restated -- what gnngls_amd.ops.greedy_edge is compared against bit for bit.  S [n,n] fp64, smaller = better; D [n,n] fp64 or
+    None.
+      keys: the key of the undirected edge {i, j}, i < j, is S[i, j] (the upper triangle alone), -0.0 and +0.0 one key; the edges are
+        sorted by (key, i, j);
+      acceptance: in that order, {i, j} is accepted iff deg[i] < 2, deg[j] < 2 and i, j are not the two ends of one path fragment;
+        after n - 1 acceptances the two nodes of degree 1 are joined: the closing edge, the n-th;
+      tour [n+1]: from depot towards the smaller-numbered of its two tour neighbours, closed at depot; score: the left-to-right sum
+        of the keys along the tour from 0.0; cost: the same sum of D[tour[p], tour[p+1]], NaN without D;
+      edges [n,2]: the accepted edges (i < j) in acceptance order, then the closing edge; rounds: what greedy_edge_rounds counts.
+    An off-diagonal entry of S that is not finite refuses the instance: status GREEDY_EDGE_BAD_SCORE, tour and edges -1, NaN score
+    and cost, rounds 0.  -> a namespace with tour, score, cost, edges, rounds, status."""
+    import numpy as np
+    depot = int(depot)
+    n, K = _greedy_edge_keys(S)
+    assert 0 <= depot < n
+    if K is None:
+        return _greedy_edge_refused(n)
+    iu, ju = np.triu_indices(n, 1)                                    # ascending (i, j)
+    order = np.argsort(K[iu, ju], kind="stable")                      # ... so a stable sort by key IS (key, i, j)
+    deg, other = [0] * n, list(range(n))
+    nbr = [[] for _ in range(n)]
+    accepted = []
+    for i, j in zip(iu[order].tolist(), ju[order].tolist()):
+        if deg[i] < 2 and deg[j] < 2 and other[i] != j:
+            a, b = other[i], other[j]
+            other[a], other[b] = b, a
+            deg[i] += 1
+            deg[j] += 1
+            nbr[i].append(j)
+            nbr[j].append(i)
+            accepted.append((i, j))
+            if len(accepted) == n - 1:
+                break
+    return _greedy_edge_result(n, K, D, depot, nbr, accepted, greedy_edge_rounds(S, depot, None).rounds)
+
+
+def greedy_edge_rounds(S, depot=0, D=None):
+    """greedy_edge in the exact parallel form the device runs (greedy_edge_kernel), restated: the same namespace, `rounds` counted
+    here.  Per node of degree < 2 a cached candidate cand[u] = the smallest edge {u, j} in (key, i, j) with deg[j] < 2, j != u and
+    j != other[u] (the far end of u's fragment) -- for a fixed u that order is (key, j).  A round
+      1. rescans the row of every end node whose cached candidate is no longer valid (validity only shrinks, so a cached minimum
+         that is still valid is still the minimum);
+      2. calls e = {u, v} dominant iff min(cand[u], cand[other[u]]) == e == min(cand[v], cand[other[v]]);
+      3. accepts all dominant edges at once;
+    until n - 1 edges are accepted.  The accepted edges, sorted by (key, i, j), are those of greedy_edge in its order: until the
+    sorted pass reaches a dominant e it accepts only smaller valid edges, none of which touches an end of e's two fragments."""
+    import numpy as np
+    depot = int(depot)
+    n, K = _greedy_edge_keys(S)
+    assert 0 <= depot < n
+    if K is None:
+        return _greedy_edge_refused(n)
+    deg, other = np.zeros(n, dtype=np.int64), np.arange(n)
+    candj, candk = np.arange(n), np.full(n, np.inf)
+    nbr = [[] for _ in range(n)]
+    accepted, rounds = [], 0
+    ids = np.arange(n)
+
+    def edge_of(u):                                                    # cand[u] as a comparable (key, i, j)
+        j = int(candj[u])
+        return (candk[u], min(u, j), max(u, j))
+
+    while len(accepted) < n - 1:
+        end = deg < 2
+        stale = end & ((deg[candj] >= 2) | (candj == other))
+        for u in np.flatnonzero(stale).tolist():
+            row = np.where(end & (ids != u) & (ids != other[u]), K[u], np.inf)
+            j = int(np.argmin(row))                                    # the first of equal keys: the lowest j
+            candj[u], candk[u] = j, row[j]
+        found = []
+        for u in np.flatnonzero(end).tolist():
+            v = int(candj[u])
+            if u < v and candj[v] == u:
+                e = edge_of(u)
+                if min(e, edge_of(int(other[u]))) == e and min(e, edge_of(int(other[v]))) == e:
+                    found.append((u, v))
+        assert found, "the smallest valid edge is dominant"
+        for u, v in found:
+            a, b = other[u], other[v]
+            other[a], other[b] = b, a
+            deg[u] += 1
+            deg[v] += 1
+            nbr[u].append(v)
+            nbr[v].append(u)
+            accepted.append((u, v))
+        rounds += 1
+    accepted.sort(key=lambda e: (K[e[0], e[1]], e[0], e[1]))
+    return _greedy_edge_result(n, K, D, depot, nbr, accepted, rounds)
+
+
 def fixed_edge_tour(G, e, scale=None, lkh_path=None, base_tour=None, label_iters=None, perturbation_moves=None, **kwargs):
     """A tour of G that holds edge e (reference __init__.py:63-79: LKH with e fixed).  Here: the fixed-edge search of
     gnngls_amd.labels on the device -- guided_local_search on G's weights with e's weight lowered by M, guide = those weights,

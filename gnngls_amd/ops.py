@@ -798,6 +798,69 @@ def beam_search(S, width, depot=0, D=None, select="score", want_beams=False, wor
     return r
 
 
+GREEDY_EDGE_MAX_N = 1024                                      # GNNGLS_GREEDY_EDGE_MAX_N
+GREEDY_EDGE_BAD_SCORE = 1                                     # GNNGLS_GREEDY_EDGE_BAD_SCORE
+GREEDY_EDGE_STALLED = 2                                       # GNNGLS_GREEDY_EDGE_STALLED
+_GREEDY_EDGE_READS = "greedy_edge_kernel reads row u of S for node u, the definition the upper triangle"
+
+
+@dataclass
+class GreedyEdgeResult:
+    tour: torch.Tensor           # [B,n+1] int32, closed at the depot, tour[1] < tour[n-1] (-1: the instance was refused)
+    score: torch.Tensor          # [B] fp64 the left-to-right sum of the edge keys along the tour
+    cost: torch.Tensor           # [B] fp64 its tour_cost on D (NaN without D)
+    edges: torch.Tensor          # [B,n,2] int32 the accepted edges (i < j) in acceptance order, then the closing edge, or None
+    rounds: torch.Tensor         # [B] int32 rounds of simultaneous acceptances the device needed (host.greedy_edge_rounds)
+    status: torch.Tensor         # [B] int32 STATUS_OK or (greedy_edge_launch only) GREEDY_EDGE_BAD_SCORE / GREEDY_EDGE_STALLED
+
+
+def greedy_edge_launch(S, depot=0, D=None, want_edges=False):
+    """The launch behind greedy_edge and torch.ops.gnngls.greedy_edge: -> GreedyEdgeResult, no synchronisation, nothing raised for
+    a refused instance (its status is GREEDY_EDGE_BAD_SCORE).  S is NOT checked for symmetry here: the caller guarantees it (a
+    matrix that is not gives an unspecified tour or GREEDY_EDGE_STALLED, never a fault)."""
+    dev = _dev()
+    B, n, n2 = S.shape
+    assert n == n2 and S.dtype == torch.float64
+    if D is not None:
+        assert D.shape == S.shape and D.dtype == torch.float64, f"D shape {tuple(D.shape)} / dtype does not match S [{B},{n},{n}] fp64"
+        D = D.contiguous()
+    L = _lib.load()
+    if not hasattr(L, "gnngls_greedy_edge"):
+        raise _lib.GnnglsHipError("this build of libgnngls_hip.so has no gnngls_greedy_edge")
+    tour = torch.empty((B, n + 1), dtype=torch.int32, device=dev)
+    score, cost = (torch.empty((B,), dtype=torch.float64, device=dev) for _ in range(2))
+    rounds, status = (torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(2))
+    edges = torch.empty((B, n, 2), dtype=torch.int32, device=dev) if want_edges else None
+    _lib.check(L.gnngls_greedy_edge(_lib.ptr(S.contiguous()), _lib.ptr(D), B, n, int(depot), _lib.ptr(tour), _lib.ptr(score), _lib.ptr(cost),
+                                    _lib.ptr(edges), _lib.ptr(rounds), _lib.ptr(status), _lib.current_stream()), "greedy_edge")
+    return GreedyEdgeResult(tour, score, cost, edges, rounds, status)
+
+
+def greedy_edge(S, depot=0, D=None, want_edges=False):
+    """Greedy edge matching ("greedy merge") of a batch in ONE launch, one workgroup per instance, n <= GREEDY_EDGE_MAX_N: the
+    edges {i, j}, i < j, in ascending (S[i,j], i, j); an edge is accepted iff both ends have degree below 2 and it closes no
+    subtour; after n - 1 acceptances the path is closed (include/gnngls_hip.h states the definition; host.greedy_edge restates it
+    in NumPy, bit for bit).  S [B,n,n] fp64 bitwise symmetric off the diagonal, smaller = better (distances, alpha, a regret
+    prediction, -log p); D [B,n,n] fp64 the distances or None.  -> GreedyEdgeResult (want_edges: with the edges in acceptance
+    order).  A matrix that is not symmetric raises before anything is launched; an instance whose S has an off-diagonal entry that
+    is not finite raises after the launch."""
+    assert S.dim() == 3 and S.shape[1] == S.shape[2] and S.dtype == torch.float64
+    raw = S.contiguous().view(torch.int64)
+    off = ~torch.eye(S.shape[1], dtype=torch.bool, device=S.device)
+    bad = ((raw != raw.transpose(1, 2)) & off).flatten(1).any(dim=1).nonzero().flatten().tolist()
+    if bad:
+        _raise_asymmetric("greedy_edge", bad, _GREEDY_EDGE_READS)
+    r = greedy_edge_launch(S, depot, D, want_edges)
+    bad = (r.status == GREEDY_EDGE_BAD_SCORE).nonzero().flatten().tolist()
+    if bad:
+        raise ValueError(f"greedy_edge: instances {bad[:8]} have a score matrix with an off-diagonal entry that is NaN or infinite "
+                         f"(status {GREEDY_EDGE_BAD_SCORE})")
+    bad = (r.status != 0).nonzero().flatten().tolist()
+    if bad:
+        _raise_asymmetric("greedy_edge", bad, _GREEDY_EDGE_READS)
+    return r
+
+
 def gls_run(D, guides, init_tour, init_cost, perturbation_moves=30, first_improvement=False,
             max_outer_iters=-1, time_limit_s=0.0, watchdog_s=None, trace_cap=0, want_trace_time=False,
             want_penalty=False, penalty_bits=0, retry_overflow=True, imp_cap=0, retry_asymmetric=True):

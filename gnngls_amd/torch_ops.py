@@ -1,7 +1,8 @@
 """PyTorch-ROCm custom operators of the hot path: `torch.ops.gnngls.*` (north_star).
 
 Ten operators and, since the Or-opt descent, iterated local search, the 3-opt descent and guided local search over Or-opt, an
-eleventh to a fourteenth, with the ant system a fifteenth and with beam search a sixteenth, are registered with
+eleventh to a fourteenth, with the ant system a fifteenth, with beam search a sixteenth and with greedy edge
+matching a seventeenth, are registered with
 `torch.library` over the C ABI of libgnngls_hip.so (include/gnngls_hip.h).  Each has
 exactly ONE implementation, for the CUDA dispatch key (= HIP on ROCm): there is no CPU kernel behind any of them, so
 calling one with CPU tensors fails in the dispatcher ("no CPU fallback" is structural, not a runtime check).  Shape
@@ -55,6 +56,10 @@ the current HIP stream, take caller-owned contiguous tensors and retain nothing.
         decoding from any edge score in one launch, n <= 1024, width <= 1024; select in {'score', 'cost'} ('cost' needs D);
         rows from n_beams on are -1 / NaN; status 1 marks an instance whose score has an off-diagonal entry that is not finite
         -- the op reports, gnngls_amd.ops.beam_search raises
+    greedy_edge(S[B,n,n] f64, D[B,n,n] f64 or None, depot) -> (tour[B,n+1] i32, score[B] f64, cost[B] f64, edges[B,n,2] i32,
+        rounds[B] i32, status[B] i32): greedy edge matching from any edge score in one launch, n <= 1024; S bitwise symmetric off
+        the diagonal (not checked here); status 1 marks an instance whose score has an off-diagonal entry that is not finite
+        -- the op reports, gnngls_amd.ops.greedy_edge raises
 """
 import ctypes
 
@@ -85,6 +90,7 @@ _LIB.define("guided_or_opt(Tensor tour, Tensor cost, Tensor D, Tensor guides, in
 _LIB.define("aco(Tensor D, Tensor H, int ants, int iters, int iter0, float rho, float min_ratio, int gb_every, bool spread_starts, int seed, "
             "Tensor? u, Tensor? tau, Tensor? best_tour, Tensor? best_cost) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("beam_search(Tensor S, Tensor? D, int width, int depot, str select) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+_LIB.define("greedy_edge(Tensor S, Tensor? D, int depot) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
 
 _workspaces = {}      # device index -> uint8 scratch tensor for the forward (grown on demand, reused across calls)
 
@@ -207,6 +213,14 @@ def _beam_search(S, D, width, depot, select):
 _LIB.impl("beam_search", _beam_search, "CUDA")
 
 
+def _greedy_edge(S, D, depot):
+    r = ops.greedy_edge_launch(S, depot, D, want_edges=True)
+    return r.tour, r.score, r.cost, r.edges, r.rounds, r.status
+
+
+_LIB.impl("greedy_edge", _greedy_edge, "CUDA")
+
+
 # ---- shape functions (fake tensors / tracing); no arithmetic -------------------------------------------------------
 @torch.library.register_fake("gnngls::regret_forward")
 def _(feat, packed_weights, n, heads, head_dim, hidden, layers):
@@ -313,3 +327,11 @@ def _(S, D, width, depot, select):
     f64 = lambda: S.new_empty((B,), dtype=torch.float64)  # noqa: E731
     return (S.new_empty((B, n + 1), dtype=torch.int32), f64(), f64(), i32(), i32(), S.new_empty((B, W, n + 1), dtype=torch.int32),
             S.new_empty((B, W), dtype=torch.float64), S.new_empty((B, W), dtype=torch.float64))
+
+
+@torch.library.register_fake("gnngls::greedy_edge")
+def _(S, D, depot):
+    B, n = S.shape[0], S.shape[1]
+    i32 = lambda: S.new_empty((B,), dtype=torch.int32)  # noqa: E731
+    f64 = lambda: S.new_empty((B,), dtype=torch.float64)  # noqa: E731
+    return S.new_empty((B, n + 1), dtype=torch.int32), f64(), f64(), S.new_empty((B, n, 2), dtype=torch.int32), i32(), i32()

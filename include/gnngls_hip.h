@@ -486,6 +486,43 @@ int gnngls_beam_search(const double *S, const double *D, int B, int n, int width
                        double *best_score, double *best_cost, int32_t *n_beams, int32_t *status, int32_t *beam_tours,
                        double *beam_score, double *beam_cost, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- greedy edge matching ("greedy merge"): decode tours from any edge score ---------------------------------------------------
+ * The other standard decoder of an edge score beside beam search, and the classical greedy constructor beside nearest neighbour
+ * and the insertions: it looks at all edges at once instead of growing one path from the depot.  The reference has no counterpart.
+ * Definition (the contract; gnngls_amd.host.greedy_edge restates it in NumPy, bit for bit).  Per instance: S [n,n] fp64 a
+ * cost-like score, smaller = better; optionally D [n,n] fp64 the distances.
+ *   Keys.  The key of the undirected edge {i, j}, i < j, is S[i, j] -- only the upper triangle defines it -- with -0.0 and +0.0 one
+ *      key.  The edges are ordered by (key, i, j): keys compare as fp64 values, ties go to the lower i, then to the lower j.
+ *   Acceptance.  Walk the edges in that order.  Every node starts with degree 0 as a path fragment of its own.  {i, j} is accepted
+ *      iff deg[i] < 2, deg[j] < 2 and i and j are not the two ends of one path fragment (it would close a subtour); it joins the
+ *      two fragments.  After n - 1 acceptances one Hamiltonian path is left; its two nodes of degree 1 are joined.  This closing
+ *      edge is the n-th edge.
+ *   Outputs.  tour [n+1]: tour[0] = tour[n] = depot, tour[1] the smaller-numbered of the depot's two tour neighbours.  score: the
+ *      left-to-right sum of the keys of the edges along tour, started from 0.0; cost: the sum of D[tour[p], tour[p+1]] in the same
+ *      order, as gnngls_tour_cost computes it, NaN without D.  edges [n,2] (optional): the n - 1 accepted edges as (i, j), i < j, in
+ *      acceptance order, then the closing edge (smaller end first).
+ *   Rounds.  The device runs the exact parallel form (gnngls_amd.host.greedy_edge_rounds restates it; DESIGN.md has the proof that
+ *      it accepts the same edges).  cand[u] of a node of degree < 2 is the smallest edge {u, j} in (key, i, j) with deg[j] < 2, j not
+ *      u and j not the far end of u's fragment; an edge e = {u, v} is dominant iff it is the smaller of the candidates of the two
+ *      ends of u's fragment and also of v's; a round accepts all dominant edges at once.  rounds is the number of rounds until
+ *      n - 1 edges are accepted: 1 <= rounds <= n - 1, a property of S alone.
+ *   Refusal.  If any off-diagonal entry of S[b] is NaN or infinite, instance b gets status GNNGLS_GREEDY_EDGE_BAD_SCORE, tour and
+ *      edges of -1, NaN score and cost, rounds 0; other instances are unaffected.  The diagonal is never used.
+ *   What is read.  Off the diagonal every entry of S is read (the refusal), and node u's candidates are taken from ROW u: S has
+ *      to be bitwise symmetric off the diagonal, which the caller guarantees (gnngls_amd.ops.greedy_edge checks it).  For a matrix
+ *      that is not, the result is unspecified but bounded: valid memory only, at most n - 1 rounds, and where a round finds no
+ *      dominant edge the instance ends with status GNNGLS_GREEDY_EDGE_STALLED and the outputs of a refusal.  D is read along the
+ *      tour only, D[tour[p], tour[p+1]].
+ *   S [B,n,n]; D [B,n,n] or NULL; tour [B,n+1] int32; score, cost [B] fp64; edges [B,n,2] int32 or NULL; rounds, status [B] int32.
+ * One workgroup of min(ceil(n / 16), 16) wavefronts per instance runs the whole decode in one launch; no workspace.
+ * 3 <= n <= GNNGLS_GREEDY_EDGE_MAX_N, B >= 1, 0 <= depot < n, no NULL pointer other than D and edges (GNNGLS_ERR_ARG): rejected on
+ * the host, with a message, before any device work. */
+#define GNNGLS_GREEDY_EDGE_MAX_N 1024
+#define GNNGLS_GREEDY_EDGE_BAD_SCORE 1
+#define GNNGLS_GREEDY_EDGE_STALLED 2
+int gnngls_greedy_edge(const double *S, const double *D, int B, int n, int depot, int32_t *tour, double *score, double *cost,
+                       int32_t *edges, int32_t *rounds, int32_t *status, void *stream);
+
 /* Host-side query (oracle/one_tree.c has no counterpart; scripts/bench_bounds.py reports it): the launch gnngls_one_tree_bound makes
  * for n nodes -- *threads workgroup size (64 = one wavefront per instance, n <= 256), *lds_bytes dynamic LDS per workgroup,
  * *nodes_per_lane register slots per lane.  Any output pointer may be NULL. */
